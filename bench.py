@@ -13,6 +13,16 @@ per-shard top-K (K*(f64,i64) per rank — latency-bound over xGMI via RCCL),
 rank 0 merges with the reference tie-break (dist total_cmp asc, id asc).
 
 Output: ONE JSON line from rank 0 (see the driver contract).
+
+A plain run does only what the headline figure needs: stage, warm up, time
+the steps, print the line. The legs that take runs of their own (the
+cpu_baseline on host cores, the HNSW gather-count calibration behind the
+persistent kernel's roofline) run only with --full. --dump-outputs DIR
+writes what the last timed step returned as DIR/<name>.npy, so two builds
+can be compared output for output (inputs are seeded: same arguments, same
+corpus and queries). The brute-force modes are bit-repeatable; in --hnsw
+mode the graph comes from the multi-threaded snapshot build, whose apply
+order is schedule-dependent, so its approximate results vary run to run.
 """
 import argparse
 import json
@@ -25,6 +35,39 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
+DUMP_MAX_BYTES = 64 << 20  # --dump-outputs cap over all arrays together
+
+
+def dump_outputs(path, result, ns):
+    """Write the last timed step's result as path/ids.npy + path/dists.npy
+    (f64; ids are < 2^53 so exact). Single query: shape (n,). Batch: shape
+    (b, k), slots past a query's result count hold id -1 / dist +inf. Over
+    the byte cap a fixed seeded sample of the batch's queries is kept, with
+    their indices in path/query_index.npy."""
+    if isinstance(result, list):  # N>1 batch: per-query merged (ids, dists)
+        b, k = len(result), max(len(r[0]) for r in result)
+        ids = np.full((b, k), -1.0)
+        dists = np.full((b, k), np.inf)
+        for j, (i_, d_) in enumerate(result):
+            ids[j, :len(i_)] = i_
+            dists[j, :len(d_)] = d_
+    else:
+        ids = np.asarray(result[0]).astype(np.float64)
+        dists = np.asarray(result[1]).astype(np.float64)
+        if ns is not None:  # batched HNSW: slots past ns[j] are unwritten
+            past = np.arange(ids.shape[1])[None, :] >= np.asarray(ns)[:, None]
+            ids[past] = -1.0
+            dists[past] = np.inf
+    arrays = {"ids": ids, "dists": dists}
+    if ids.nbytes + dists.nbytes > DUMP_MAX_BYTES:
+        keep = max(DUMP_MAX_BYTES // (2 * ids[0].nbytes + 8), 1)
+        pick = np.sort(np.random.default_rng(0x5DB1).choice(
+            len(ids), size=keep, replace=False))
+        arrays = {"ids": ids[pick], "dists": dists[pick],
+                  "query_index": pick.astype(np.float64)}
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def main():
@@ -58,7 +101,16 @@ def main():
                     help="row bound for the cpu_baseline leg (defaults to "
                          "the full workload at the default size: no "
                          "extrapolation)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the cpu_baseline leg")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beyond the headline figure: "
+                         "cpu_baseline (oracle on host cores) and, in HNSW "
+                         "mode, the gather-count calibration for the "
+                         "persistent kernel's roofline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's "
+                         "result to DIR/ids.npy and DIR/dists.npy (f64)")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -141,6 +193,7 @@ def main():
     queries = gen_f32(0xBEEF, 0, min(nq, 4096), args.dim)
 
     device = torch.device(f"cuda:{local_rank}")
+    last_ns = [None]  # batched HNSW: per-query result counts of the last step
 
     def one_batch(si):
         """One step of the batched path: args.batch concurrent queries."""
@@ -173,6 +226,7 @@ def main():
         q0 = (si * b) % max(len(queries) - b, 1)
         ids, dists, ns = hnsw_index.knn_search_batch(queries[q0:q0 + b],
                                                      args.k, args.ef)
+        last_ns[0] = ns
         if world > 1:
             # per-query merge across shard replicas (same protocol as the
             # brute-force batch path; HNSW shards queries over replicas of
@@ -243,9 +297,10 @@ def main():
     # hnsw-batch roofline calibration: the persistent kernel does not count
     # its gathered rows, but it visits exactly the per-hop path's set (same
     # best-first queue), so sample the per-hop gather count per query here,
-    # outside the timed region.
+    # outside the timed region. Runs of its own: --full only (without it the
+    # persistent kernel's line carries no roofline).
     hnsw_gather_avg = None
-    if args.hnsw and not args.hnsw_perhop:
+    if args.full and args.hnsw and not args.hnsw_perhop:
         tot = 0
         nsample = min(32, len(queries))
         for j in range(nsample):
@@ -258,12 +313,13 @@ def main():
         dist.barrier()
     torch.cuda.synchronize(device) if torch.cuda.is_available() else None
     step_times = []
+    result = None
     scan_ms_acc = 0.0
     rows_scanned_acc = 0
     t_begin = time.perf_counter()
     for i in range(args.steps):
         ts = time.perf_counter()
-        one_query(args.warmup + i)
+        result = one_query(args.warmup + i)
         step_times.append(time.perf_counter() - ts)
         st = ctx.stats()
         scan_ms_acc += st["last_scan_kernel_ms"]
@@ -281,6 +337,10 @@ def main():
 
     if rank != 0:
         return
+
+    if args.dump_outputs and result is not None:
+        dump_outputs(args.dump_outputs, result,
+                     last_ns[0] if world == 1 else None)
 
     queries_per_step = max(args.batch, 1)
     qps = args.steps * queries_per_step / t_total
@@ -317,7 +377,9 @@ def main():
         else:
             alg_bytes = (rows_scanned_acc / args.steps) * args.dim * 4
         achieved_gbs = alg_bytes / (scan_ms_avg * 1e-3) / 1e9
-        roofline = {
+        live_count = args.batch == 0 and (args.hnsw_perhop or args.ef > 512)
+        calibrated = live_count or hnsw_gather_avg is not None
+        roofline = None if not calibrated else {
             "bound": "hbm",
             "achieved": round(achieved_gbs, 1),
             "peak": HBM_PEAK_GBS,
@@ -341,7 +403,8 @@ def main():
 
     # --- cpu_baseline: the oracle (kind "port") on host cores, rank0/N=1 ---
     cpu_baseline = None
-    if args.hnsw and world == 1 and not args.no_cpu_baseline:
+    want_cpu = args.full and world == 1 and not args.no_cpu_baseline
+    if args.hnsw and want_cpu:
         # oracle HNSW search over the EXACT graph the GPU searched: the
         # product graph exports layer by layer into orc_hnsw_import (the
         # oracle stays the checker/baseline — it never feeds the product
@@ -393,7 +456,7 @@ def main():
             "kind": "port",
             "sample": sample,
         }
-    elif world == 1 and not args.no_cpu_baseline:
+    elif want_cpu:
         import oracle
         srows = min(args.cpu_sample_rows, rows)
         sample = oracle.gen_f32(args.seed, 0, srows, args.dim)
@@ -405,8 +468,8 @@ def main():
         reps = 3
         used = 0
         for r in range(reps):
-            _, _, used = oracle.topk_f32_mt(args.metric, sample,
-                                            queries[r + 1], args.k)
+            _, _, used = oracle.topk_f32_mt(
+                args.metric, sample, queries[(r + 1) % len(queries)], args.k)
         t_cpu_sample = (time.perf_counter() - tcs) / reps
         t_cpu_full = t_cpu_sample * (rows / srows)
         cpu_baseline = {
