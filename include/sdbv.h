@@ -80,11 +80,16 @@ enum {
 typedef struct sdbv_ctx sdbv_ctx; /* owns HIP stream, device pools, staged tables */
 
 typedef struct sdbv_stats {
-	double last_scan_kernel_ms;  /* HIP-event time of the last distance-scan kernel */
-	double last_merge_kernel_ms; /* HIP-event time of the last top-K merge kernel */
+	double last_scan_kernel_ms;  /* HIP-event time of the last call's distance-producing
+	                                kernels (scan; or prefilter + compact + rescore) */
+	double last_merge_kernel_ms; /* HIP-event time of the last call's top-K selects */
 	double last_total_ms;        /* host wall of the last search call (incl. D2H of K results) */
 	uint64_t bytes_staged;       /* device bytes held by staged tables */
 	uint64_t last_rows_scanned;  /* rows the last scan covered */
+	uint64_t last_prefilter_candidates; /* rows the last prefilter passed to the
+	                                       exact rescore (0 on the exact scan) */
+	uint32_t last_scan_path; /* sdbv_knn_bruteforce: 0 = exact scan, 1 = prefilter,
+	                            2 = prefilter overflowed, then exact scan */
 } sdbv_stats;
 
 /* Create a context on HIP device `device` (-1 = current device). */
@@ -101,7 +106,15 @@ int sdbv_get_stats(sdbv_ctx *, sdbv_stats *out);
  * must be strictly increasing (NULL => 0..n-1); result tie-break is
  * (distance asc, id asc), which equals the reference's orderings for
  * monotone ids (knn.rs:363 BTreeSet<(FloatKey, VectorId)>, knn_topk.rs:61-73
- * insertion-order seq). Restages (replaces) if `table` already staged. */
+ * insertion-order seq). Restages (replaces) if `table` already staged.
+ *
+ * Memory: d*4 + 20 B per row. A COSINE table of at least
+ * SDBV_SCAN_PREFILTER_MIN_ROWS rows (environment, default 500000) also gets
+ * the single-query prefilter's bf16 shadow, d*2 + 4 B per row more (+50 %),
+ * unless the environment sets SDBV_SCAN_PREFILTER=0 or the allocation
+ * fails: then the table simply has no shadow and staging still succeeds.
+ * The shadow never changes a result (see sdbv_knn_bruteforce). Tables staged
+ * for graph search (sdbv_hnsw_finalize, sdbv_index_*) never get one. */
 int sdbv_stage_corpus(sdbv_ctx *, uint64_t table, const float *rows,
                       const uint64_t *ids, uint64_t n, uint32_t d,
                       uint8_t metric);
@@ -114,6 +127,17 @@ int sdbv_stage_corpus(sdbv_ctx *, uint64_t table, const float *rows,
 int sdbv_stage_synthetic(sdbv_ctx *, uint64_t table, uint64_t n, uint32_t d,
                          uint8_t metric, uint64_t seed, uint64_t row_offset,
                          uint64_t id_base);
+
+/* Build (on != 0) or free (on == 0) a staged cosine table's prefilter shadow
+ * explicitly, regardless of the staging policy — for tests and for A/B in
+ * one process. SDBV_ERR_UNSUPPORTED for non-cosine tables, SDBV_ERR_OOM when
+ * the shadow does not fit (the table stays usable without it). */
+int sdbv_table_set_prefilter(sdbv_ctx *, uint64_t table, int on);
+/* Host-only: the proven bound on |exact - prefilter| cosine distance at
+ * dimension d, and f32 -> bf16 round-to-nearest-even (returned as f32) as
+ * the shadow is built. */
+float sdbv_prefilter_eps(uint32_t d);
+float sdbv_bf16_rne(float x);
 
 uint64_t sdbv_table_rows(sdbv_ctx *, uint64_t table);
 int sdbv_drop_table(sdbv_ctx *, uint64_t table);
@@ -134,7 +158,16 @@ void sdbv_gen_f32(uint64_t seed, uint64_t row0, uint64_t nrows, uint32_t d,
  * k <= 64 runs fully on-device (block-local exact top-K); larger k
  * (the reference accepts any) takes one all-distances launch + exact host
  * selection — same ordering contract, costing an n-f64 transfer.
- * *out_n = min(k, n). */
+ * *out_n = min(k, n).
+ *
+ * On a cosine table with a prefilter shadow (k <= 64, finite query with a
+ * norm in [2^-30, 2^30]) the call streams the bf16 shadow (half the bytes),
+ * keeps every row within twice the proven bound sdbv_prefilter_eps(d) of
+ * the Kth approximate distance, and recomputes those rows with the exact
+ * chain. Exactness guarantee: ids and distance bits equal the exact scan's
+ * for every input — rows the bound cannot cover are always recomputed, and
+ * a query with more than 16384 candidates reruns the exact scan
+ * (sdbv_stats.last_scan_path tells which path ran). */
 int sdbv_knn_bruteforce(sdbv_ctx *, uint64_t table, const float *q, uint32_t d,
                         uint32_t k, uint64_t *out_ids, double *out_dists,
                         uint32_t *out_n);

@@ -52,6 +52,8 @@ class _Stats(ctypes.Structure):
         ("last_total_ms", ctypes.c_double),
         ("bytes_staged", ctypes.c_uint64),
         ("last_rows_scanned", ctypes.c_uint64),
+        ("last_prefilter_candidates", ctypes.c_uint64),
+        ("last_scan_path", ctypes.c_uint32),
     ]
 
 
@@ -85,6 +87,11 @@ def lib():
     L.sdbv_table_rows.restype = u64
     L.sdbv_table_rows.argtypes = [vp, u64]
     L.sdbv_drop_table.argtypes = [vp, u64]
+    L.sdbv_table_set_prefilter.argtypes = [vp, u64, ctypes.c_int]
+    L.sdbv_prefilter_eps.restype = ctypes.c_float
+    L.sdbv_prefilter_eps.argtypes = [u32]
+    L.sdbv_bf16_rne.restype = ctypes.c_float
+    L.sdbv_bf16_rne.argtypes = [ctypes.c_float]
     L.sdbv_knn_bruteforce.argtypes = [vp, u64, f32p, u32, u32, u64p, f64p, u32p]
     L.sdbv_all_distances.argtypes = [vp, u64, f32p, u32, f64p]
     L.sdbv_gather_distance.argtypes = [vp, u64, u32p, u32, f32p, u32, f64p]
@@ -235,6 +242,12 @@ class Context:
     def drop_table(self, table):
         _check(self._ptr, lib().sdbv_drop_table(self._ptr, table), "drop_table")
 
+    def table_set_prefilter(self, table, on):
+        """Build (on) or free (off) the table's bf16 prefilter shadow,
+        regardless of the staging policy (cosine tables only)."""
+        _check(self._ptr, lib().sdbv_table_set_prefilter(
+            self._ptr, table, int(bool(on))), "sdbv_table_set_prefilter")
+
     def knn_bruteforce(self, table, q, k):
         import numpy as np
         q = np.ascontiguousarray(q, dtype=np.float32)
@@ -300,6 +313,16 @@ class Context:
             dists.ctypes.data_as(ctypes.POINTER(ctypes.c_double))),
             "sdbv_knn_batch")
         return ids, dists
+
+
+def prefilter_eps(d):
+    """Proven bound on |exact - prefilter| cosine distance at dimension d."""
+    return float(lib().sdbv_prefilter_eps(d))
+
+
+def bf16_rne(x):
+    """f32 -> bf16 round-to-nearest-even, returned as f32 (host-only)."""
+    return float(lib().sdbv_bf16_rne(float(x)))
 
 
 def hnsw_create_host(d, metric="euclidean", m=12, m0=None, efc=150,

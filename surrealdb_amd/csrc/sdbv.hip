@@ -89,6 +89,13 @@ struct Table {
 	float *aux = nullptr;     // per-row f32 selection key aux for the batch
 	                          // path: cosine 1/norm, euclidean sum-of-squares
 	uint64_t *ids_dev = nullptr; // per-row id, device (merge kernel maps)
+	// single-query prefilter (cosine only, optional): bf16 shadow of cm,
+	// feature-major [d][sn_pad], rounded to nearest-even, and the per-row
+	// f32 1/norm (NaN marks a row the error bound cannot cover)
+	uint16_t *shadow = nullptr;
+	float *pinv = nullptr;
+	uint64_t sn_pad = 0;
+	uint64_t shadow_bytes = 0;
 	uint64_t bytes = 0;
 };
 
@@ -107,7 +114,14 @@ struct sdbv_ctx {
 	float *q_dev = nullptr;
 	float *q_pin = nullptr; // pinned H2D staging for the per-query upload
 	uint32_t q_cap = 0;
-	hipEvent_t ev0, ev1, ev2;
+	hipEvent_t ev0, ev1, ev2, ev3, ev4;
+	// single-query prefilter scratch
+	float *pf_scores = nullptr; // [sn_pad] approximate distances
+	uint64_t pf_scores_cap = 0;
+	uint32_t *pf_rows = nullptr; // [PF_CAND_CAP] candidate rows
+	void *pf_cands = nullptr;    // [PF_CAND_CAP] rescored Cand
+	void *pf_res = nullptr;      // [MAX_K + 2] Cand: top-k, the count, counter
+	uint64_t pf_slots = 0;       // k_prefilter blocks the device holds at once
 	// batched path
 	rocblas_handle blas = nullptr;
 	float *S = nullptr; // chunk scores scratch, [chunk][b] col-major
@@ -467,7 +481,7 @@ __global__ __launch_bounds__(THREADS) void k_scan(
 // total is the classic single-block merge; a two-level tree (G slices,
 // then one block over G*k) cuts the 1954-block scan's merge latency
 // (top-k of per-slice top-ks == the global top-k, exactly).
-__global__ __launch_bounds__(THREADS) void k_merge(
+__device__ __forceinline__ static void merge_slice(
     Cand *__restrict__ block_out, uint64_t total, uint32_t k,
     uint64_t per_block, Cand *__restrict__ out) {
 	__shared__ uint64_t red_key[THREADS / 64];
@@ -540,6 +554,401 @@ __global__ __launch_bounds__(THREADS) void k_merge(
 		}
 		__syncthreads();
 	}
+}
+
+__global__ __launch_bounds__(THREADS) void k_merge(
+    Cand *__restrict__ block_out, uint64_t total, uint32_t k,
+    uint64_t per_block, Cand *__restrict__ out) {
+	merge_slice(block_out, total, k, per_block, out);
+}
+
+// ---------------------------------------------------------------------------
+// Single-query cosine prefilter: stream a bf16 shadow of the corpus (half the
+// bytes of the f32 store), keep every row whose approximate distance could
+// reach the top K under the proven bound pf_eps(d), and recompute only those
+// rows with the exact restated chain. Results are bit-identical to k_scan<0>
+// by construction: the approximate scores only decide WHICH rows get the
+// exact chain, never a result value or an order.
+// ---------------------------------------------------------------------------
+#define PF_ROWS_PER_LANE 8
+#define PF_TILE (THREADS * PF_ROWS_PER_LANE) /* 2048 rows per block-sweep */
+#define PF_CAND_CAP 16384u
+#define PF_RESCORE_BLOCKS 2048
+// Norm window (rows and query) in which neither chain can overflow and
+// underflow stays negligible: |x_k| <= norm <= 2^30, so every product is
+// <= 2^60 and every partial sum <= MAX_D * 2^60 < 2^73; norm products are
+// >= 2^-60, so the <= 2^-149 absolute error of an underflowed product or
+// of a bf16-subnormal rounding is < 2^-75 in cosine units.
+#define PF_NORM_MIN 0x1p-30
+#define PF_NORM_MAX 0x1p30
+
+// Upper 16 bits of a FINITE f32 rounded to nearest-even bf16 (a carry out of
+// the mantissa propagates into the exponent; 0x7F80 = overflowed to inf).
+__host__ __device__ static inline uint32_t pf_bf16_bits(uint32_t u) {
+	return (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
+}
+
+// Bound on |exact - approx| for a row and a query inside the norm window,
+// exact = the restated f32 chain with its f64 finish (k_scan<0>),
+// approx = 1 - s~ * inv_q * inv_i in f32 over the bf16 shadow (k_prefilter).
+// In cosine units, i.e. divided by |x||q|, with u = 2^-24:
+//  - quantisation: bf16 keeps 8 significant bits, so round-to-nearest moves
+//    x_k by at most 2^-8 |x_k| (unit roundoff 2^-8, not 2^-9); by
+//    Cauchy-Schwarz |sum (x~_k - x_k) q_k| <= 2^-8 |x||q|.
+//  - accumulation: a d-term f32 dot in any order, fused or mul-then-add, is
+//    within gamma(d + 8) <= 1.001 (d + 8) u of its exact sum relative to
+//    sum |x_k q_k| <= |x||q| (the + 8 covers the partial-sum combine and the
+//    product roundings of the unfused chain); the shadow chain's terms are
+//    up to (1 + 2^-8) larger. Both chains: <= 2.006 (d + 8) u.
+//  - norms: both sides divide by the SAME computed norms, which are within
+//    (d + 8) u of the true ones, so the two terms above grow by at most
+//    1 + 2 (d + 8) u <= 1.0005. The factor 1.01 below covers all of these.
+//  - finish: inv_q, inv_i and the two f32 products round 4 times (4.1 u on
+//    |cos| <= 1.001), the final subtraction rounds a value below 2.01
+//    (<= 2u), f64 steps are ~2^-52: together < 7u < 2^-21. 2^-20 leaves the
+//    rest for the underflow terms bounded at PF_NORM_MIN.
+// Holds for every d <= MAX_D (e(4096) ~ 0.0044).
+__host__ __device__ static inline float pf_eps(uint32_t d) {
+	return 1.01f * (0x1p-8f + 2.0f * (float)(d + 8) * 0x1p-24f) + 0x1p-20f;
+}
+
+// f32 total order key and its inverse (same construction as d_total_key).
+__device__ static inline uint32_t d_key32(float x) {
+	uint32_t b = __float_as_uint(x);
+	return (b >> 31) ? ~b : (b | 0x80000000u);
+}
+__device__ static inline float d_unkey32(uint32_t k) {
+	return __uint_as_float((k >> 31) ? (k & 0x7FFFFFFFu) : ~k);
+}
+
+// Build the shadow: one lane converts 8 consecutive rows per feature (two
+// float4 loads, one 16-byte store). pinv[r] = f32 1/norm, or NaN when the
+// bound cannot cover row r: a non-finite element, a bf16 rounding that
+// overflows, a norm outside [PF_NORM_MIN, PF_NORM_MAX] (zero and non-finite
+// norms included), or a padding row.
+__global__ void k_shadow(const float *__restrict__ cm,
+                         const double *__restrict__ norms,
+                         uint16_t *__restrict__ sh, float *__restrict__ pinv,
+                         uint64_t n, uint64_t n_pad, uint64_t sn_pad,
+                         uint32_t d) {
+	uint64_t r0 = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) *
+	              PF_ROWS_PER_LANE;
+	if (r0 >= sn_pad)
+		return;
+	const bool in_cm = r0 < n_pad; // n_pad % 8 == 0: a group is all in or out
+	uint32_t bad = 0;
+	for (uint32_t k = 0; k < d; k++) {
+		float4 a = make_float4(0.f, 0.f, 0.f, 0.f), b = a;
+		if (in_cm) {
+			a = *(const float4 *)(cm + (uint64_t)k * n_pad + r0);
+			b = *(const float4 *)(cm + (uint64_t)k * n_pad + r0 + 4);
+		}
+		const float v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+		uint32_t h[8];
+#pragma unroll
+		for (int c = 0; c < 8; c++) {
+			uint32_t u = __float_as_uint(v[c]);
+			h[c] = pf_bf16_bits(u) & 0xFFFFu;
+			if ((u & 0x7F800000u) == 0x7F800000u ||
+			    (h[c] & 0x7F80u) == 0x7F80u)
+				bad |= 1u << c;
+		}
+		uint4 o;
+		o.x = h[0] | (h[1] << 16);
+		o.y = h[2] | (h[3] << 16);
+		o.z = h[4] | (h[5] << 16);
+		o.w = h[6] | (h[7] << 16);
+		*(uint4 *)(sh + (uint64_t)k * sn_pad + r0) = o;
+	}
+#pragma unroll
+	for (int c = 0; c < 8; c++) {
+		uint64_t r = r0 + c;
+		float inv = __uint_as_float(0x7FC00000u); // NaN = always rescore
+		if (r < n && !((bad >> c) & 1u)) {
+			double nm = norms[r];
+			if (nm >= PF_NORM_MIN && nm <= PF_NORM_MAX)
+				inv = (float)(1.0 / nm);
+		}
+		pinv[r] = inv;
+	}
+}
+
+// Block-wide exact k-selection of the smallest packed (key32 << 32 | row)
+// values (all distinct, all < ~0); same hand-off discipline as
+// block_select_topk.
+__device__ static void pf_block_select(uint64_t *buf, int total,
+                                       uint64_t *topk, int k, int *out_n) {
+	__shared__ uint64_t red_v[THREADS / 64];
+	__shared__ int red_i[THREADS / 64];
+	const int lane = threadIdx.x & 63;
+	const int wave = threadIdx.x >> 6;
+	int out = total < k ? total : k;
+	for (int slot = 0; slot < out; slot++) {
+		uint64_t bv = ~0ULL;
+		int bi = -1;
+		for (int i = threadIdx.x; i < total; i += THREADS) {
+			uint64_t cv = buf[i];
+			if (cv < bv) {
+				bv = cv;
+				bi = i;
+			}
+		}
+		for (int off = 32; off > 0; off >>= 1) {
+			uint64_t ov = __shfl_down(bv, off);
+			int oi = __shfl_down(bi, off);
+			if (ov < bv) {
+				bv = ov;
+				bi = oi;
+			}
+		}
+		if (lane == 0) {
+			red_v[wave] = bv;
+			red_i[wave] = bi;
+		}
+		__syncthreads();
+		if (threadIdx.x == 0) {
+			uint64_t bbv = ~0ULL;
+			int best = -1;
+			for (int w = 0; w < THREADS / 64; w++)
+				if (red_i[w] >= 0 && red_v[w] < bbv) {
+					bbv = red_v[w];
+					best = red_i[w];
+				}
+			topk[slot] = bbv;
+			buf[best] = ~0ULL;
+		}
+		__syncthreads();
+	}
+	*out_n = out;
+}
+
+// The k_scan skeleton over the shadow: contiguous row spans per block, 8
+// rows per lane from one 16-byte load per feature, unpack by shift, f32 FMA
+// accumulation, a_i = 1 - s~ * inv_q * inv_i stored to scores[] and fed to
+// the block top-K. Rows the bound cannot cover (pinv NaN) and non-finite
+// scores are stored as -inf, so k_pf_compact always passes them on, and are
+// kept OUT of the top-K: the threshold must come from K rows that do carry
+// the bound. Block 0 also clears the candidate counter for k_pf_compact.
+__global__ __launch_bounds__(THREADS) void k_prefilter(
+    const uint16_t *__restrict__ sh, const float *__restrict__ pinv,
+    uint64_t n, uint64_t sn_pad, uint32_t d, const float *__restrict__ qg,
+    float inv_qnorm, uint32_t k, uint64_t rows_per_block,
+    float *__restrict__ scores, Cand *__restrict__ block_out,
+    uint32_t *__restrict__ cand_cnt) {
+	__shared__ uint64_t buf[PF_TILE + MAX_K];
+	__shared__ uint64_t topk[MAX_K];
+	__shared__ int cnt;
+	__shared__ int topk_n;
+	__shared__ uint64_t kth;
+
+	if (threadIdx.x == 0) {
+		cnt = 0;
+		topk_n = 0;
+		kth = ~0ULL;
+		if (blockIdx.x == 0)
+			*cand_cnt = 0;
+	}
+	__syncthreads();
+
+	uint64_t row_begin = (uint64_t)blockIdx.x * rows_per_block;
+	uint64_t row_end = row_begin + rows_per_block;
+	if (row_end > n)
+		row_end = n;
+	const float ninf = __uint_as_float(0xFF800000u);
+
+	for (uint64_t tile_base = row_begin; tile_base < row_end;
+	     tile_base += PF_TILE) {
+		const uint64_t r0 =
+		    tile_base + (uint64_t)threadIdx.x * PF_ROWS_PER_LANE;
+		const uint16_t *p = sh + r0;
+		float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#define PF_ACC(V, qk)                                                          \
+	acc[0] = __fmaf_rn(__uint_as_float((V).x << 16), qk, acc[0]);              \
+	acc[1] = __fmaf_rn(__uint_as_float((V).x & 0xFFFF0000u), qk, acc[1]);      \
+	acc[2] = __fmaf_rn(__uint_as_float((V).y << 16), qk, acc[2]);              \
+	acc[3] = __fmaf_rn(__uint_as_float((V).y & 0xFFFF0000u), qk, acc[3]);      \
+	acc[4] = __fmaf_rn(__uint_as_float((V).z << 16), qk, acc[4]);              \
+	acc[5] = __fmaf_rn(__uint_as_float((V).z & 0xFFFF0000u), qk, acc[5]);      \
+	acc[6] = __fmaf_rn(__uint_as_float((V).w << 16), qk, acc[6]);              \
+	acc[7] = __fmaf_rn(__uint_as_float((V).w & 0xFFFF0000u), qk, acc[7]);
+		uint32_t kk = 0;
+		for (; kk + 8 <= d; kk += 8) {
+			uint4 w[8];
+#pragma unroll
+			for (uint32_t j = 0; j < 8; j++)
+				w[j] = *(const uint4 *)(p + (uint64_t)(kk + j) * sn_pad);
+#pragma unroll
+			for (uint32_t j = 0; j < 8; j++) {
+				const float qk = qg[kk + j]; // uniform: scalar load
+				PF_ACC(w[j], qk)
+			}
+		}
+		for (; kk < d; kk++) {
+			const uint4 w1 = *(const uint4 *)(p + (uint64_t)kk * sn_pad);
+			const float qk = qg[kk];
+			PF_ACC(w1, qk)
+		}
+#undef PF_ACC
+		const float4 i0 = *(const float4 *)(pinv + r0);
+		const float4 i1 = *(const float4 *)(pinv + r0 + 4);
+		const float inv[8] = {i0.x, i0.y, i0.z, i0.w, i1.x, i1.y, i1.z, i1.w};
+		float a[8];
+		bool ok[8];
+#pragma unroll
+		for (int c = 0; c < 8; c++) {
+			float s = 1.0f - acc[c] * inv_qnorm * inv[c];
+			ok[c] = (r0 + c) < row_end &&
+			        (__float_as_uint(s) & 0x7F800000u) != 0x7F800000u;
+			a[c] = ok[c] ? s : ninf;
+		}
+		*(float4 *)(scores + r0) = make_float4(a[0], a[1], a[2], a[3]);
+		*(float4 *)(scores + r0 + 4) = make_float4(a[4], a[5], a[6], a[7]);
+
+		// threshold check + candidate append (rare path)
+		const uint64_t kthv = kth;
+		const int full = (topk_n >= (int)k);
+#pragma unroll
+		for (int c = 0; c < 8; c++) {
+			if (!ok[c])
+				continue;
+			uint64_t v = ((uint64_t)d_key32(a[c]) << 32) | (uint32_t)(r0 + c);
+			if (!full || v < kthv) {
+				int idx = atomicAdd(&cnt, 1);
+				buf[idx] = v;
+			}
+		}
+		__syncthreads();
+
+		if (cnt > 0) {
+			int m = cnt;
+			for (int i = threadIdx.x; i < topk_n; i += THREADS)
+				buf[m + i] = topk[i];
+			int total = m + topk_n;
+			__syncthreads();
+			int new_n;
+			pf_block_select(buf, total, topk, (int)k, &new_n);
+			if (threadIdx.x == 0) {
+				topk_n = new_n;
+				if (new_n >= (int)k)
+					kth = topk[k - 1];
+				cnt = 0;
+			}
+		}
+		__syncthreads();
+	}
+
+	// block winners as Cand{approx distance, row} (pad with +inf) so the
+	// existing k_merge selects the K smallest approximate distances
+	if (threadIdx.x < k) {
+		Cand c;
+		if ((int)threadIdx.x < topk_n) {
+			c.dist = (double)d_unkey32((uint32_t)(topk[threadIdx.x] >> 32));
+			c.id = (uint32_t)topk[threadIdx.x];
+		} else {
+			c.dist = __longlong_as_double(0x7FF0000000000000LL); // +inf
+			c.id = ~0ULL;
+		}
+		block_out[(uint64_t)blockIdx.x * k + threadIdx.x] = c;
+	}
+}
+
+// One pass over scores[]: append every row with a_i <= A_K + 2e to the
+// candidate list. approx_top[k-1].dist is A_K (+inf when fewer than K rows
+// carry the bound: then every row passes). The counter keeps counting past
+// PF_CAND_CAP; the list is never written past it.
+__global__ void k_pf_compact(const float *__restrict__ scores, uint64_t n,
+                             const Cand *__restrict__ approx_top, uint32_t k,
+                             float eps, uint32_t *__restrict__ cand_cnt,
+                             uint32_t *__restrict__ cand_rows) {
+	const double thr = approx_top[k - 1].dist + 2.0 * (double)eps;
+	const uint64_t ngrp = (n + 3) / 4;
+	for (uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	     g < ngrp; g += (uint64_t)gridDim.x * blockDim.x) {
+		const float4 s = *(const float4 *)(scores + g * 4);
+		const float v[4] = {s.x, s.y, s.z, s.w};
+#pragma unroll
+		for (int c = 0; c < 4; c++) {
+			uint64_t r = g * 4 + c;
+			if (r < n && (double)v[c] <= thr) {
+				uint32_t idx = atomicAdd(cand_cnt, 1u);
+				if (idx < PF_CAND_CAP)
+					cand_rows[idx] = (uint32_t)r;
+			}
+		}
+	}
+}
+
+// Exact rescore, one workgroup per candidate (grid-stride over the device
+// count): all lanes fetch the row's d strided f32 elements into LDS, then
+// the op sequence of k_scan<0> / k_gather_dist<0> runs on them: 8 partial
+// sums, the same combine, the same tail, the f64 finish with norms[r].
+__global__ __launch_bounds__(64) void k_pf_rescore(
+    const float *__restrict__ cm, const double *__restrict__ norms,
+    const uint64_t *__restrict__ ids, uint64_t n_pad, uint32_t d,
+    const float *__restrict__ qg, double q_norm,
+    const uint32_t *__restrict__ cand_cnt,
+    const uint32_t *__restrict__ cand_rows, Cand *__restrict__ out) {
+	__shared__ float qs[MAX_D];
+	__shared__ float xs[MAX_D];
+	__shared__ float ps[8];
+	const uint32_t cnt = *cand_cnt;
+	if (cnt > PF_CAND_CAP || blockIdx.x >= cnt)
+		return; // overflow: the host reruns the exact scan
+	for (uint32_t i = threadIdx.x; i < d; i += 64)
+		qs[i] = qg[i];
+	for (uint32_t c = blockIdx.x; c < cnt; c += gridDim.x) {
+		__syncthreads();
+		const uint32_t r = cand_rows[c];
+		for (uint32_t i = threadIdx.x; i < d; i += 64)
+			xs[i] = cm[(uint64_t)i * n_pad + r];
+		__syncthreads();
+		// the chain's 8 partial sums are independent of each other: lane j
+		// runs partial j's own sequence, lane 0 then combines them in the
+		// chain's order — the same operations on the same values
+		const uint32_t d8 = d & ~7u;
+		if (threadIdx.x < 8) {
+			float pj = 0.f;
+			for (uint32_t i = threadIdx.x; i < d8; i += 8)
+				pj = __fadd_rn(pj, __fmul_rn(xs[i], qs[i]));
+			ps[threadIdx.x] = pj;
+		}
+		__syncthreads();
+		if (threadIdx.x == 0) {
+			float p[8];
+#pragma unroll
+			for (int j = 0; j < 8; j++)
+				p[j] = ps[j];
+			uint32_t k8 = d8;
+			float sum = 0.f;
+			sum = __fadd_rn(sum, __fadd_rn(p[0], p[4]));
+			sum = __fadd_rn(sum, __fadd_rn(p[1], p[5]));
+			sum = __fadd_rn(sum, __fadd_rn(p[2], p[6]));
+			sum = __fadd_rn(sum, __fadd_rn(p[3], p[7]));
+			for (; k8 < d; k8++)
+				sum = __fadd_rn(sum, __fmul_rn(xs[k8], qs[k8]));
+			double den = q_norm * norms[r];
+			Cand o;
+			o.dist = 1.0 - (double)sum / den;
+			o.id = ids[r];
+			out[c] = o;
+		}
+	}
+}
+
+// Final select over the rescored candidates: k_merge's (total_cmp dist, id)
+// order with the candidate count read on the device. The raw count lands
+// right behind the k results so one D2H copy carries both; an overflowed
+// count selects nothing (the host reruns the exact scan).
+__global__ __launch_bounds__(THREADS) void k_pf_final(
+    Cand *__restrict__ cands, const uint32_t *__restrict__ cand_cnt,
+    uint32_t k, Cand *__restrict__ out) {
+	const uint32_t raw = *cand_cnt;
+	const uint64_t total = raw > PF_CAND_CAP ? 0 : raw;
+	if (threadIdx.x == 0) {
+		out[k].dist = 0.0;
+		out[k].id = raw;
+	}
+	merge_slice(cands, total, k, total, out);
 }
 
 // All-distance kernel: one lane per row, feature-major coalesced reads.
@@ -1797,6 +2206,10 @@ static void free_table(Table &t) {
 		(void)hipFree(t.aux);
 	if (t.ids_dev)
 		(void)hipFree(t.ids_dev);
+	if (t.shadow)
+		(void)hipFree(t.shadow);
+	if (t.pinv)
+		(void)hipFree(t.pinv);
 	t = Table{};
 }
 
@@ -1823,6 +2236,8 @@ int sdbv_init(int device, sdbv_ctx **out) {
 	(void)hipEventCreate(&ctx->ev0);
 	(void)hipEventCreate(&ctx->ev1);
 	(void)hipEventCreate(&ctx->ev2);
+	(void)hipEventCreate(&ctx->ev3);
+	(void)hipEventCreate(&ctx->ev4);
 	*out = ctx;
 	return SDBV_OK;
 }
@@ -1840,6 +2255,10 @@ void sdbv_shutdown(sdbv_ctx *ctx) {
 		(void)hipFree(ctx->merge_tmp);
 	if (ctx->q_dev)
 		(void)hipFree(ctx->q_dev);
+	for (void *p : {(void *)ctx->pf_scores, (void *)ctx->pf_rows,
+	                ctx->pf_cands, ctx->pf_res})
+		if (p)
+			(void)hipFree(p);
 	for (void *p : {(void *)ctx->S, ctx->bstate, (void *)ctx->Q_dev,
 	                (void *)ctx->qnorms, (void *)ctx->bdists,
 	                (void *)ctx->btheta, (void *)ctx->bcand,
@@ -1851,6 +2270,8 @@ void sdbv_shutdown(sdbv_ctx *ctx) {
 	(void)hipEventDestroy(ctx->ev0);
 	(void)hipEventDestroy(ctx->ev1);
 	(void)hipEventDestroy(ctx->ev2);
+	(void)hipEventDestroy(ctx->ev3);
+	(void)hipEventDestroy(ctx->ev4);
 	(void)hipStreamDestroy(ctx->stream);
 	delete ctx;
 }
@@ -1896,7 +2317,82 @@ static int stage_common(sdbv_ctx *ctx, uint64_t table, uint64_t n, uint32_t d,
 	return SDBV_OK;
 }
 
-static int finish_stage(sdbv_ctx *ctx, Table *t) {
+static void refresh_bytes_staged(sdbv_ctx *ctx) {
+	uint64_t total = 0;
+	for (auto &kv : ctx->tables)
+		total += kv.second.bytes;
+	ctx->stats.bytes_staged = total;
+}
+
+static void free_shadow(sdbv_ctx *ctx, Table *t) {
+	if (t->shadow)
+		(void)hipFree(t->shadow);
+	if (t->pinv)
+		(void)hipFree(t->pinv);
+	t->shadow = nullptr;
+	t->pinv = nullptr;
+	t->bytes -= t->shadow_bytes;
+	t->shadow_bytes = 0;
+	t->sn_pad = 0;
+	refresh_bytes_staged(ctx);
+}
+
+// Build the prefilter shadow of a staged cosine table (norms already
+// computed, in stream order). +50 % device memory; a failed allocation leaves
+// the table without a shadow and returns SDBV_ERR_OOM.
+static int build_shadow(sdbv_ctx *ctx, Table *t) {
+	if (t->metric != SDBV_METRIC_COSINE)
+		return SDBV_ERR_UNSUPPORTED;
+	if (t->shadow)
+		return SDBV_OK;
+	uint64_t sn_pad = ((t->n + PF_TILE - 1) / PF_TILE) * PF_TILE;
+	if (sn_pad == 0)
+		sn_pad = PF_TILE;
+	uint64_t sh_bytes = (uint64_t)t->d * sn_pad * sizeof(uint16_t);
+	uint64_t pi_bytes = sn_pad * sizeof(float);
+	if (hipMalloc(&t->shadow, sh_bytes) != hipSuccess ||
+	    hipMalloc(&t->pinv, pi_bytes) != hipSuccess) {
+		(void)hipGetLastError(); // allocation failure is not sticky
+		if (t->shadow)
+			(void)hipFree(t->shadow);
+		t->shadow = nullptr;
+		t->pinv = nullptr;
+		return SDBV_ERR_OOM;
+	}
+	t->sn_pad = sn_pad;
+	t->shadow_bytes = sh_bytes + pi_bytes;
+	t->bytes += t->shadow_bytes;
+	uint64_t groups = sn_pad / PF_ROWS_PER_LANE;
+	hipLaunchKernelGGL(k_shadow, dim3((uint32_t)((groups + 255) / 256)),
+	                   dim3(256), 0, ctx->stream, t->cm, t->norms, t->shadow,
+	                   t->pinv, t->n, t->n_pad, sn_pad, t->d);
+	HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+	HIP_CHECK(ctx, hipGetLastError());
+	refresh_bytes_staged(ctx);
+	return SDBV_OK;
+}
+
+// Default minimum row count from which scan staging builds the shadow: the
+// measured crossover (profiles/prefilter_scan.md) below which the extra
+// launches of the prefilter path cost more than the halved stream saves.
+#define PF_DEFAULT_MIN_ROWS 500000ull
+
+// Staging policy: SDBV_SCAN_PREFILTER=0 opts out;
+// SDBV_SCAN_PREFILTER_MIN_ROWS overrides the default minimum row count.
+static bool shadow_policy(const Table *t) {
+	if (t->metric != SDBV_METRIC_COSINE)
+		return false;
+	const char *e = getenv("SDBV_SCAN_PREFILTER");
+	if (e && e[0] == '0' && e[1] == 0)
+		return false;
+	uint64_t min_rows = PF_DEFAULT_MIN_ROWS;
+	const char *m = getenv("SDBV_SCAN_PREFILTER_MIN_ROWS");
+	if (m && *m)
+		min_rows = strtoull(m, nullptr, 10);
+	return t->n >= min_rows;
+}
+
+static int finish_stage(sdbv_ctx *ctx, Table *t, bool scan_table) {
 	uint64_t nb = (t->n + THREADS - 1) / THREADS;
 	if (t->metric == SDBV_METRIC_COSINE) {
 		hipLaunchKernelGGL(k_norms, dim3((uint32_t)nb), dim3(THREADS), 0,
@@ -1913,16 +2409,23 @@ static int finish_stage(sdbv_ctx *ctx, Table *t) {
 	}
 	HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
 	HIP_CHECK(ctx, hipGetLastError());
-	uint64_t total = 0;
-	for (auto &kv : ctx->tables)
-		total += kv.second.bytes;
-	ctx->stats.bytes_staged = total;
+	refresh_bytes_staged(ctx);
+	// a table staged for scanning gets the prefilter shadow when the policy
+	// asks for one; without the memory for it the table simply has none
+	if (scan_table && shadow_policy(t)) {
+		int rc = build_shadow(ctx, t);
+		if (rc != SDBV_OK && rc != SDBV_ERR_OOM)
+			return rc;
+	}
 	return SDBV_OK;
 }
 
-int sdbv_stage_corpus(sdbv_ctx *ctx, uint64_t table, const float *rows,
-                      const uint64_t *ids, uint64_t n, uint32_t d,
-                      uint8_t metric) {
+// Internal staging entry. scan_table = false stages for graph search
+// (sdbv_hnsw_finalize): such a table is never scanned per query, so it never
+// pays the shadow's +50 % HBM.
+static int stage_corpus_impl(sdbv_ctx *ctx, uint64_t table, const float *rows,
+                             const uint64_t *ids, uint64_t n, uint32_t d,
+                             uint8_t metric, bool scan_table) {
 	std::lock_guard<std::mutex> lk(ctx->mu);
 	// tie-break contract: ids must be strictly increasing (see include/sdbv.h)
 	if (ids)
@@ -1949,9 +2452,42 @@ int sdbv_stage_corpus(sdbv_ctx *ctx, uint64_t table, const float *rows,
 		hipLaunchKernelGGL(k_fill_ids, dim3((uint32_t)nb), dim3(THREADS), 0,
 		                   ctx->stream, t->ids_dev, t->n_pad, 0);
 	}
-	int rc2 = finish_stage(ctx, t);
+	int rc2 = finish_stage(ctx, t, scan_table);
 	(void)hipFree(rm);
 	return rc2;
+}
+
+int sdbv_stage_corpus(sdbv_ctx *ctx, uint64_t table, const float *rows,
+                      const uint64_t *ids, uint64_t n, uint32_t d,
+                      uint8_t metric) {
+	return stage_corpus_impl(ctx, table, rows, ids, n, d, metric, true);
+}
+
+int sdbv_table_set_prefilter(sdbv_ctx *ctx, uint64_t table, int on) {
+	std::lock_guard<std::mutex> lk(ctx->mu);
+	auto it = ctx->tables.find(table);
+	if (it == ctx->tables.end())
+		return SDBV_ERR_NO_TABLE;
+	Table *t = &it->second;
+	if (t->metric != SDBV_METRIC_COSINE)
+		return SDBV_ERR_UNSUPPORTED;
+	if (on)
+		return build_shadow(ctx, t);
+	if (t->shadow)
+		free_shadow(ctx, t);
+	return SDBV_OK;
+}
+
+float sdbv_prefilter_eps(uint32_t d) { return pf_eps(d); }
+
+float sdbv_bf16_rne(float x) {
+	uint32_t u;
+	std::memcpy(&u, &x, 4);
+	if ((u & 0x7F800000u) == 0x7F800000u)
+		return x; // inf and NaN pass through
+	u = pf_bf16_bits(u) << 16;
+	std::memcpy(&x, &u, 4);
+	return x;
 }
 
 int sdbv_stage_synthetic(sdbv_ctx *ctx, uint64_t table, uint64_t n, uint32_t d,
@@ -1967,7 +2503,7 @@ int sdbv_stage_synthetic(sdbv_ctx *ctx, uint64_t table, uint64_t n, uint32_t d,
 	uint64_t nb = (t->n_pad + THREADS - 1) / THREADS;
 	hipLaunchKernelGGL(k_fill_ids, dim3((uint32_t)nb), dim3(THREADS), 0,
 	                   ctx->stream, t->ids_dev, t->n_pad, id_base);
-	return finish_stage(ctx, t);
+	return finish_stage(ctx, t, true);
 }
 
 uint64_t sdbv_table_rows(sdbv_ctx *ctx, uint64_t table) {
@@ -1983,6 +2519,7 @@ int sdbv_drop_table(sdbv_ctx *ctx, uint64_t table) {
 		return SDBV_ERR_NO_TABLE;
 	free_table(it->second);
 	ctx->tables.erase(it);
+	refresh_bytes_staged(ctx);
 	return SDBV_OK;
 }
 
@@ -2116,39 +2653,135 @@ static int knn_large_k(sdbv_ctx *ctx, Table &t, const float *q, uint32_t d,
 	return SDBV_OK;
 }
 
-int sdbv_knn_bruteforce(sdbv_ctx *ctx, uint64_t table, const float *q,
-                        uint32_t d, uint32_t k, uint64_t *out_ids,
-                        double *out_dists, uint32_t *out_n) {
-	std::lock_guard<std::mutex> lk(ctx->mu);
-	auto it = ctx->tables.find(table);
-	if (it == ctx->tables.end())
-		return SDBV_ERR_NO_TABLE;
-	Table &t = it->second;
-	if (d != t.d)
-		return SDBV_ERR_BAD_ARG;
-	if (k == 0 || k > (1u << 22))
-		return SDBV_ERR_BAD_ARG;
-	if (k > MAX_K || t.metric > SDBV_METRIC_EUCLIDEAN)
-		return knn_large_k(ctx, t, q, d, k, out_ids, out_dists, out_n);
-
-	// pick a grid: >=2048 blocks to fill 256 CUs, contiguous spans per block
-	uint64_t tiles = (t.n + TILE - 1) / TILE;
-	uint64_t nblocks = tiles < 2048 ? tiles : 2048;
+// Row-span grid of the prefilter sweep: contiguous spans of PF_TILE-row
+// tiles, sized so that the whole grid is resident at once (one round, every
+// block the same span). A grid of a few more blocks than the chip holds runs
+// a second, mostly empty round with too few bytes in flight per CU — 3.5 %
+// of the kernel at 10M rows (profiles/prefilter_scan.md).
+static uint64_t prefilter_grid(sdbv_ctx *ctx, uint64_t n,
+                               uint64_t *rows_per_block) {
+	if (ctx->pf_slots == 0) {
+		int per_cu = 0, cus = 0;
+		if (hipOccupancyMaxActiveBlocksPerMultiprocessor(
+		        &per_cu, k_prefilter, THREADS, 0) != hipSuccess ||
+		    hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount,
+		                          ctx->device) != hipSuccess ||
+		    per_cu <= 0 || cus <= 0) {
+			(void)hipGetLastError();
+			ctx->pf_slots = 2048;
+		} else {
+			ctx->pf_slots = (uint64_t)per_cu * (uint64_t)cus;
+		}
+	}
+	uint64_t tiles = (n + PF_TILE - 1) / PF_TILE;
+	uint64_t nblocks = tiles < ctx->pf_slots ? tiles : ctx->pf_slots;
 	if (nblocks == 0)
 		nblocks = 1;
 	uint64_t tiles_per_block = (tiles + nblocks - 1) / nblocks;
-	uint64_t rows_per_block = tiles_per_block * TILE;
-	nblocks = (t.n + rows_per_block - 1) / rows_per_block;
+	*rows_per_block = tiles_per_block * PF_TILE;
+	return (n + *rows_per_block - 1) / *rows_per_block;
+}
 
-	int rc = ensure_query_scratch(ctx, d, nblocks, k);
-	if (rc != SDBV_OK)
-		return rc;
-	std::memcpy(ctx->q_pin, q, d * sizeof(float)); // pinned staging
-	HIP_CHECK(ctx, hipMemcpyAsync(ctx->q_dev, ctx->q_pin, d * sizeof(float),
-	                              hipMemcpyHostToDevice, ctx->stream));
-	double q_norm = sqrt((double)h_sumsq_f32(q, d));
+// The prefilter path of sdbv_knn_bruteforce (cosine, k <= MAX_K, table with
+// a shadow, query inside the norm window; q already in ctx->q_dev and the
+// query scratch sized for prefilter_grid). host_out[0..k) receives the
+// exact top-k, *ncand the candidate count; *ncand > PF_CAND_CAP means the
+// list overflowed and host_out is void: the caller runs the exact scan.
+// One D2H copy and one sync, like the exact path. Caller holds ctx->mu.
+static int knn_prefilter(sdbv_ctx *ctx, Table &t, uint32_t k, double q_norm,
+                         Cand *host_out, uint32_t *ncand) {
+	if (ctx->pf_scores_cap < t.sn_pad) {
+		if (ctx->pf_scores)
+			(void)hipFree(ctx->pf_scores);
+		ctx->pf_scores = nullptr;
+		ctx->pf_scores_cap = 0;
+		HIP_CHECK(ctx, hipMalloc(&ctx->pf_scores, t.sn_pad * sizeof(float)));
+		ctx->pf_scores_cap = t.sn_pad;
+	}
+	if (!ctx->pf_rows)
+		HIP_CHECK(ctx, hipMalloc(&ctx->pf_rows,
+		                         PF_CAND_CAP * sizeof(uint32_t)));
+	if (!ctx->pf_cands)
+		HIP_CHECK(ctx, hipMalloc(&ctx->pf_cands, PF_CAND_CAP * sizeof(Cand)));
+	if (!ctx->pf_res)
+		HIP_CHECK(ctx, hipMalloc(&ctx->pf_res, (MAX_K + 2) * sizeof(Cand)));
 
-	auto t_start = std::chrono::steady_clock::now();
+	uint64_t rows_per_block = 0;
+	uint64_t nblocks = prefilter_grid(ctx, t.n, &rows_per_block);
+	Cand *res = (Cand *)ctx->pf_res;
+	// device counter: behind the k results and the copy of the count that
+	// k_pf_final appends to them
+	uint32_t *cand_cnt = (uint32_t *)&res[MAX_K + 1];
+	const float inv_q = (float)(1.0 / q_norm);
+
+	HIP_CHECK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+	hipLaunchKernelGGL(k_prefilter, dim3((uint32_t)nblocks), dim3(THREADS), 0,
+	                   ctx->stream, t.shadow, t.pinv, t.n, t.sn_pad, t.d,
+	                   ctx->q_dev, inv_q, k, rows_per_block, ctx->pf_scores,
+	                   (Cand *)ctx->block_out, cand_cnt);
+	HIP_CHECK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+	{
+		// K smallest approximate distances -> final_out (A_K = entry k-1)
+		uint64_t total = nblocks * k;
+		const uint64_t G = 32;
+		if (total > 4096 && nblocks > G) {
+			uint64_t per = ((nblocks + G - 1) / G) * k;
+			hipLaunchKernelGGL(k_merge, dim3((uint32_t)G), dim3(THREADS),
+			                   0, ctx->stream, (Cand *)ctx->block_out,
+			                   total, k, per, (Cand *)ctx->merge_tmp);
+			hipLaunchKernelGGL(k_merge, dim3(1), dim3(THREADS), 0,
+			                   ctx->stream, (Cand *)ctx->merge_tmp, G * k,
+			                   k, G * k, (Cand *)ctx->final_out);
+		} else {
+			hipLaunchKernelGGL(k_merge, dim3(1), dim3(THREADS), 0,
+			                   ctx->stream, (Cand *)ctx->block_out, total,
+			                   k, total, (Cand *)ctx->final_out);
+		}
+	}
+	HIP_CHECK(ctx, hipEventRecord(ctx->ev2, ctx->stream));
+	{
+		uint64_t ngrp = (t.n + 3) / 4;
+		uint64_t nb = (ngrp + THREADS - 1) / THREADS;
+		if (nb > 2048)
+			nb = 2048;
+		if (nb == 0)
+			nb = 1;
+		hipLaunchKernelGGL(k_pf_compact, dim3((uint32_t)nb), dim3(THREADS), 0,
+		                   ctx->stream, ctx->pf_scores, t.n,
+		                   (const Cand *)ctx->final_out, k, pf_eps(t.d),
+		                   cand_cnt, ctx->pf_rows);
+		hipLaunchKernelGGL(k_pf_rescore, dim3(PF_RESCORE_BLOCKS), dim3(64), 0,
+		                   ctx->stream, t.cm, t.norms, t.ids_dev, t.n_pad,
+		                   t.d, ctx->q_dev, q_norm, cand_cnt, ctx->pf_rows,
+		                   (Cand *)ctx->pf_cands);
+	}
+	HIP_CHECK(ctx, hipEventRecord(ctx->ev3, ctx->stream));
+	hipLaunchKernelGGL(k_pf_final, dim3(1), dim3(THREADS), 0, ctx->stream,
+	                   (Cand *)ctx->pf_cands, cand_cnt, k, res);
+	HIP_CHECK(ctx, hipEventRecord(ctx->ev4, ctx->stream));
+	HIP_CHECK(ctx, hipMemcpyAsync(host_out, res, (k + 1) * sizeof(Cand),
+	                              hipMemcpyDeviceToHost, ctx->stream));
+	HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+	HIP_CHECK(ctx, hipGetLastError());
+	*ncand = (uint32_t)host_out[k].id;
+
+	float ms_pre = 0, ms_sel = 0, ms_rescore = 0, ms_final = 0;
+	(void)hipEventElapsedTime(&ms_pre, ctx->ev0, ctx->ev1);
+	(void)hipEventElapsedTime(&ms_sel, ctx->ev1, ctx->ev2);
+	(void)hipEventElapsedTime(&ms_rescore, ctx->ev2, ctx->ev3);
+	(void)hipEventElapsedTime(&ms_final, ctx->ev3, ctx->ev4);
+	ctx->stats.last_scan_kernel_ms = (double)ms_pre + ms_rescore;
+	ctx->stats.last_merge_kernel_ms = (double)ms_sel + ms_final;
+	ctx->stats.last_rows_scanned = t.n;
+	return SDBV_OK;
+}
+
+// The exact scan of sdbv_knn_bruteforce: k_scan over the f32 store, then the
+// tree merge; host_out[0..k) receives the top-k. q already in ctx->q_dev.
+// Caller holds ctx->mu.
+static int knn_exact_scan(sdbv_ctx *ctx, Table &t, uint32_t k, double q_norm,
+                          uint64_t nblocks, uint64_t rows_per_block,
+                          Cand *host_out) {
 	HIP_CHECK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
 	if (t.metric == SDBV_METRIC_COSINE)
 		hipLaunchKernelGGL(k_scan<0>, dim3((uint32_t)nblocks), dim3(THREADS), 0,
@@ -2181,7 +2814,6 @@ int sdbv_knn_bruteforce(sdbv_ctx *ctx, uint64_t table, const float *q,
 		}
 	}
 	HIP_CHECK(ctx, hipEventRecord(ctx->ev2, ctx->stream));
-	Cand host_out[MAX_K];
 	HIP_CHECK(ctx, hipMemcpyAsync(host_out, ctx->final_out, k * sizeof(Cand),
 	                              hipMemcpyDeviceToHost, ctx->stream));
 	HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
@@ -2193,6 +2825,66 @@ int sdbv_knn_bruteforce(sdbv_ctx *ctx, uint64_t table, const float *q,
 	ctx->stats.last_scan_kernel_ms = ms_scan;
 	ctx->stats.last_merge_kernel_ms = ms_merge;
 	ctx->stats.last_rows_scanned = t.n;
+	return SDBV_OK;
+}
+
+int sdbv_knn_bruteforce(sdbv_ctx *ctx, uint64_t table, const float *q,
+                        uint32_t d, uint32_t k, uint64_t *out_ids,
+                        double *out_dists, uint32_t *out_n) {
+	std::lock_guard<std::mutex> lk(ctx->mu);
+	auto it = ctx->tables.find(table);
+	if (it == ctx->tables.end())
+		return SDBV_ERR_NO_TABLE;
+	Table &t = it->second;
+	if (d != t.d)
+		return SDBV_ERR_BAD_ARG;
+	if (k == 0 || k > (1u << 22))
+		return SDBV_ERR_BAD_ARG;
+	ctx->stats.last_scan_path = 0;
+	ctx->stats.last_prefilter_candidates = 0;
+	if (k > MAX_K || t.metric > SDBV_METRIC_EUCLIDEAN)
+		return knn_large_k(ctx, t, q, d, k, out_ids, out_dists, out_n);
+
+	// pick a grid: >=2048 blocks to fill 256 CUs, contiguous spans per block
+	uint64_t tiles = (t.n + TILE - 1) / TILE;
+	uint64_t nblocks = tiles < 2048 ? tiles : 2048;
+	if (nblocks == 0)
+		nblocks = 1;
+	uint64_t tiles_per_block = (tiles + nblocks - 1) / nblocks;
+	uint64_t rows_per_block = tiles_per_block * TILE;
+	nblocks = (t.n + rows_per_block - 1) / rows_per_block;
+
+	uint64_t pf_rows_per_block = 0;
+	uint64_t scratch_blocks =
+	    std::max(nblocks, prefilter_grid(ctx, t.n, &pf_rows_per_block));
+	int rc = ensure_query_scratch(ctx, d, scratch_blocks, k);
+	if (rc != SDBV_OK)
+		return rc;
+	std::memcpy(ctx->q_pin, q, d * sizeof(float)); // pinned staging
+	HIP_CHECK(ctx, hipMemcpyAsync(ctx->q_dev, ctx->q_pin, d * sizeof(float),
+	                              hipMemcpyHostToDevice, ctx->stream));
+	double q_norm = sqrt((double)h_sumsq_f32(q, d));
+
+	auto t_start = std::chrono::steady_clock::now();
+	Cand host_out[MAX_K + 1];
+	// Prefilter path: a shadowed cosine table and a query whose norm lies in
+	// the window the bound is proven for (a non-finite element makes the
+	// norm non-finite). Everything else, and a query whose candidate list
+	// overflowed, takes the exact scan; results never depend on the choice.
+	if (t.shadow && q_norm >= PF_NORM_MIN && q_norm <= PF_NORM_MAX) {
+		uint32_t ncand = 0;
+		rc = knn_prefilter(ctx, t, k, q_norm, host_out, &ncand);
+		if (rc != SDBV_OK)
+			return rc;
+		ctx->stats.last_prefilter_candidates = ncand;
+		ctx->stats.last_scan_path = ncand <= PF_CAND_CAP ? 1 : 2;
+	}
+	if (ctx->stats.last_scan_path != 1) {
+		rc = knn_exact_scan(ctx, t, k, q_norm, nblocks, rows_per_block,
+		                    host_out);
+		if (rc != SDBV_OK)
+			return rc;
+	}
 	ctx->stats.last_total_ms =
 	    std::chrono::duration<double, std::milli>(
 	        std::chrono::steady_clock::now() - t_start)
@@ -4674,8 +5366,8 @@ int sdbv_hnsw_finalize(sdbv_hnsw *h, uint64_t table) {
 	if (!h || !h->ctx || h->next_id == 0)
 		return SDBV_ERR_BAD_ARG;
 	hnsw_free_device_state(h);
-	int rc = sdbv_stage_corpus(h->ctx, table, h->vecs.data(), nullptr,
-	                           h->next_id, h->d, h->metric);
+	int rc = stage_corpus_impl(h->ctx, table, h->vecs.data(), nullptr,
+	                           h->next_id, h->d, h->metric, false);
 	if (rc)
 		return rc;
 	sdbv_ctx *ctx = h->ctx;
