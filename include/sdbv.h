@@ -88,8 +88,10 @@ typedef struct sdbv_stats {
 	uint64_t last_rows_scanned;  /* rows the last scan covered */
 	uint64_t last_prefilter_candidates; /* rows the last prefilter passed to the
 	                                       exact rescore (0 on the exact scan) */
-	uint32_t last_scan_path; /* sdbv_knn_bruteforce: 0 = exact scan, 1 = prefilter,
-	                            2 = prefilter overflowed, then exact scan */
+	uint32_t last_scan_path; /* sdbv_knn_bruteforce: 0 = exact scan, 1 = bf16
+	                            prefilter, 2 = bf16 prefilter overflowed, then
+	                            exact scan, 3 = int8 prefilter, 4 = int8
+	                            prefilter overflowed, then exact scan */
 } sdbv_stats;
 
 /* Create a context on HIP device `device` (-1 = current device). */
@@ -110,11 +112,16 @@ int sdbv_get_stats(sdbv_ctx *, sdbv_stats *out);
  *
  * Memory: d*4 + 20 B per row. A COSINE table of at least
  * SDBV_SCAN_PREFILTER_MIN_ROWS rows (environment, default 500000) also gets
- * the single-query prefilter's bf16 shadow, d*2 + 4 B per row more (+50 %),
- * unless the environment sets SDBV_SCAN_PREFILTER=0 or the allocation
- * fails: then the table simply has no shadow and staging still succeeds.
- * The shadow never changes a result (see sdbv_knn_bruteforce). Tables staged
- * for graph search (sdbv_hnsw_finalize, sdbv_index_*) never get one. */
+ * a single-query prefilter shadow, unless the environment sets
+ * SDBV_SCAN_PREFILTER=0 or the allocation fails: then the table simply has
+ * no shadow and staging still succeeds. The shadow is the int8 one, d + 8 B
+ * per row more (+25 %), if the table also has at least
+ * SDBV_SCAN_PREFILTER_I8_MIN_ROWS rows (environment, default 500000,
+ * independent of the first threshold) and SDBV_SCAN_PREFILTER_I8 is not 0;
+ * otherwise the bf16 one, d*2 + 4 B per row more (+50 %). A table holds at
+ * most one shadow. The shadow never changes a result (see
+ * sdbv_knn_bruteforce). Tables staged for graph search (sdbv_hnsw_finalize,
+ * sdbv_index_*) never get one. */
 int sdbv_stage_corpus(sdbv_ctx *, uint64_t table, const float *rows,
                       const uint64_t *ids, uint64_t n, uint32_t d,
                       uint8_t metric);
@@ -128,16 +135,31 @@ int sdbv_stage_synthetic(sdbv_ctx *, uint64_t table, uint64_t n, uint32_t d,
                          uint8_t metric, uint64_t seed, uint64_t row_offset,
                          uint64_t id_base);
 
-/* Build (on != 0) or free (on == 0) a staged cosine table's prefilter shadow
- * explicitly, regardless of the staging policy — for tests and for A/B in
- * one process. SDBV_ERR_UNSUPPORTED for non-cosine tables, SDBV_ERR_OOM when
- * the shadow does not fit (the table stays usable without it). */
+/* Build (on != 0) the bf16 prefilter shadow of a staged cosine table, or free
+ * (on == 0) whichever shadow it has, explicitly, regardless of the staging
+ * policy — for tests and for A/B in one process. SDBV_ERR_UNSUPPORTED for
+ * non-cosine tables, SDBV_ERR_OOM when the shadow does not fit (the table
+ * stays usable without it). */
 int sdbv_table_set_prefilter(sdbv_ctx *, uint64_t table, int on);
+/* The same with the kind spelled out: 0 = none, 1 = bf16, 2 = int8 (codes in
+ * [-127, 127] with one f32 scale per row, plus the row's own proven error
+ * bound: d + 8 B per row). Setting a kind frees a shadow of the other kind. */
+int sdbv_table_set_prefilter_kind(sdbv_ctx *, uint64_t table, int kind);
 /* Host-only: the proven bound on |exact - prefilter| cosine distance at
  * dimension d, and f32 -> bf16 round-to-nearest-even (returned as f32) as
  * the shadow is built. */
 float sdbv_prefilter_eps(uint32_t d);
 float sdbv_bf16_rne(float x);
+/* Host-only: quantise one row of d <= 4096 f32 elements for the int8 shadow
+ * exactly as staging does. norm = the row's staged norm (sqrt of the restated
+ * f32 sum-of-squares chain, in f64). codes[k] = rint(x[k] / scale) in
+ * [-127, 127], *scale = f32(maxabs / 127), *eps = the proven bound on
+ * |exact - prefilter| cosine distance of THIS row for any query with a norm
+ * in [2^-30, 2^30]. A row the bound cannot cover (non-finite element, norm
+ * outside [2^-30, 2^30]) gets zero codes, *scale = NaN and *eps = 0: the
+ * prefilter always recomputes such a row. */
+int sdbv_prefilter_i8_row(const float *x, uint32_t d, double norm,
+                          int8_t *codes, float *scale, float *eps);
 
 uint64_t sdbv_table_rows(sdbv_ctx *, uint64_t table);
 int sdbv_drop_table(sdbv_ctx *, uint64_t table);
@@ -161,10 +183,12 @@ void sdbv_gen_f32(uint64_t seed, uint64_t row0, uint64_t nrows, uint32_t d,
  * *out_n = min(k, n).
  *
  * On a cosine table with a prefilter shadow (k <= 64, finite query with a
- * norm in [2^-30, 2^30]) the call streams the bf16 shadow (half the bytes),
- * keeps every row within twice the proven bound sdbv_prefilter_eps(d) of
- * the Kth approximate distance, and recomputes those rows with the exact
- * chain. Exactness guarantee: ids and distance bits equal the exact scan's
+ * norm in [2^-30, 2^30]) the call streams the shadow instead of the f32
+ * store: bf16 (half the bytes), keeping every row within twice the proven
+ * bound sdbv_prefilter_eps(d) of the Kth approximate distance; or int8 (a
+ * quarter), keeping every row whose approximate distance minus its own
+ * proven bound does not exceed the Kth smallest approximate distance plus
+ * bound. It recomputes those rows with the exact chain. Exactness guarantee: ids and distance bits equal the exact scan's
  * for every input — rows the bound cannot cover are always recomputed, and
  * a query with more than 16384 candidates reruns the exact scan
  * (sdbv_stats.last_scan_path tells which path ran). */

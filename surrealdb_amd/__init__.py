@@ -88,6 +88,10 @@ def lib():
     L.sdbv_table_rows.argtypes = [vp, u64]
     L.sdbv_drop_table.argtypes = [vp, u64]
     L.sdbv_table_set_prefilter.argtypes = [vp, u64, ctypes.c_int]
+    L.sdbv_table_set_prefilter_kind.argtypes = [vp, u64, ctypes.c_int]
+    L.sdbv_prefilter_i8_row.argtypes = [f32p, u32, ctypes.c_double,
+                                        ctypes.POINTER(ctypes.c_int8), f32p,
+                                        f32p]
     L.sdbv_prefilter_eps.restype = ctypes.c_float
     L.sdbv_prefilter_eps.argtypes = [u32]
     L.sdbv_bf16_rne.restype = ctypes.c_float
@@ -248,6 +252,12 @@ class Context:
         _check(self._ptr, lib().sdbv_table_set_prefilter(
             self._ptr, table, int(bool(on))), "sdbv_table_set_prefilter")
 
+    def table_set_prefilter_kind(self, table, kind):
+        """Give the table the prefilter shadow of this kind (0 none, 1 bf16,
+        2 int8), freeing a shadow of another kind."""
+        _check(self._ptr, lib().sdbv_table_set_prefilter_kind(
+            self._ptr, table, int(kind)), "sdbv_table_set_prefilter_kind")
+
     def knn_bruteforce(self, table, q, k):
         import numpy as np
         q = np.ascontiguousarray(q, dtype=np.float32)
@@ -318,6 +328,22 @@ class Context:
 def prefilter_eps(d):
     """Proven bound on |exact - prefilter| cosine distance at dimension d."""
     return float(lib().sdbv_prefilter_eps(d))
+
+
+def prefilter_i8_row(x, norm):
+    """Quantise one f32 row for the int8 prefilter shadow as staging does
+    (host-only): (codes int8[d], scale f32, eps f32). norm is the row's
+    staged f64 norm; scale is NaN for a row the bound cannot cover."""
+    import numpy as np
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    codes = np.empty(x.size, dtype=np.int8)
+    scale = ctypes.c_float(0.0)
+    eps = ctypes.c_float(0.0)
+    _check(None, lib().sdbv_prefilter_i8_row(
+        x.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), x.size, float(norm),
+        codes.ctypes.data_as(ctypes.POINTER(ctypes.c_int8)),
+        ctypes.byref(scale), ctypes.byref(eps)), "sdbv_prefilter_i8_row")
+    return codes, np.float32(scale.value), np.float32(eps.value)
 
 
 def bf16_rne(x):

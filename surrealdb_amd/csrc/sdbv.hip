@@ -94,6 +94,13 @@ struct Table {
 	// f32 1/norm (NaN marks a row the error bound cannot cover)
 	uint16_t *shadow = nullptr;
 	float *pinv = nullptr;
+	// or, instead of the bf16 shadow (a table holds at most one): int8
+	// codes, bias-128 bytes, feature-major [d][sn_pad], with per row
+	// pscale = scale/norm (NaN marks an uncovered row) and the row's proven
+	// bound peps; pscale and peps share one allocation
+	uint8_t *shadow8 = nullptr;
+	float *pscale = nullptr;
+	float *peps = nullptr;
 	uint64_t sn_pad = 0;
 	uint64_t shadow_bytes = 0;
 	uint64_t bytes = 0;
@@ -122,6 +129,7 @@ struct sdbv_ctx {
 	void *pf_cands = nullptr;    // [PF_CAND_CAP] rescored Cand
 	void *pf_res = nullptr;      // [MAX_K + 2] Cand: top-k, the count, counter
 	uint64_t pf_slots = 0;       // k_prefilter blocks the device holds at once
+	uint64_t pf8_slots = 0;      // the same for k_prefilter_i8
 	// batched path
 	rocblas_handle blas = nullptr;
 	float *S = nullptr; // chunk scores scratch, [chunk][b] col-major
@@ -852,9 +860,276 @@ __global__ __launch_bounds__(THREADS) void k_prefilter(
 	}
 }
 
-// One pass over scores[]: append every row with a_i <= A_K + 2e to the
-// candidate list. approx_top[k-1].dist is A_K (+inf when fewer than K rows
-// carry the bound: then every row passes). The counter keeps counting past
+// ---------------------------------------------------------------------------
+// Int8 tier of the prefilter: a quarter of the f32 store's bytes. Row r is
+// stored as symmetric codes c_k in [-127, 127] with one f32 scale_r =
+// maxabs_r / 127, as bias-128 bytes b_k = c_k + 128 so that one
+// v_cvt_f32_ubyteN unpacks an element; the kernel accumulates sum b_k q_k
+// and removes 128 * sum q_k once per row. Each row carries its own proven
+// bound peps[r] (below) instead of the global pf_eps(d).
+// ---------------------------------------------------------------------------
+#define PF8_ROWS_PER_LANE 16
+#define PF8_TILE (THREADS * PF8_ROWS_PER_LANE) /* 4096 rows per block-sweep */
+
+// Quantise one row (elements x[k * xstride], k < d; norm = the row's staged
+// f64 norm) and derive its bound. The one routine behind both k_shadow_i8
+// and sdbv_prefilter_i8_row. Writes the d stored bytes to codes[k * cstride],
+// *scale, *pscale = f32(scale / norm) and *eps. A row the bound cannot cover
+// (a non-finite element, a norm outside [PF_NORM_MIN, PF_NORM_MAX], which
+// includes the zero row and a non-finite norm) gets zero codes (byte 128),
+// scale = pscale = NaN and eps = 0: the prefilter always rescores it.
+//
+// Bound on |exact - approx| for a covered row and a query inside the norm
+// window, exact = the restated f32 chain with its f64 finish (k_scan<0>),
+// approx = 1 - (t - B) * inv_q * pscale in f32 (k_prefilter_i8), where
+// t = the sequential f32 FMA chain over b_k q_k and B = f32(128 sum q_k).
+// In cosine units, i.e. divided by |x||q|, with u = 2^-24:
+//  - quantisation: |sum (x_k - scale c_k) q_k| <= |x - scale c| |q| by
+//    Cauchy-Schwarz, i.e. rho = |x - scale c| / |x|, the row's ACTUAL
+//    residual: computed here in f64 from the f32 elements and the products
+//    scale * c_k (31 significant bits: exact in f64) and rounded up
+//    (the d + 3 f64 roundings are below 2^-40 relative).
+//  - exact chain: within 1.001 (d + 8) u of its exact sum relative to
+//    sum |x_k q_k| <= |x||q|, as for pf_eps.
+//  - approx chain: t carries d FMA roundings on terms b_k |q_k| <= 255 |q_k|:
+//    |t - sum b_k q_k| <= 1.001 d u 255 |q|_1. B is an f64 sum rounded once
+//    to f32: <= 1.001 u 128 |q|_1. The subtraction t - B rounds once on
+//    |sum c_k q_k| + the above <= 1.01 * 127 |q|_1. Together
+//    <= 1.001 (d + 2) u 255 |q|_1, and |q|_1 <= sqrt(d) |q|. Scaled by
+//    scale / |x| = maxabs / (127 |x|) this is
+//    <= 2.012 (d + 2) u sqrt(d) maxabs / |x| in cosine units: the price of
+//    the cancelled bias, per row because it depends on maxabs_r / norm_r.
+//  - norms: rho and maxabs / |x| are taken against the computed norm, both
+//    chains divide by the same computed norms, within (d + 8) u of the true
+//    ones: the factor 1.01 covers it, as for pf_eps.
+//  - finish: |approx cosine| <= 1 + rho <= 1.26 (each element is within
+//    scale / 2 of its product, so rho <= sqrt(d) / 254 <= 0.252 at MAX_D);
+//    scale, pscale, inv_q and the two f32 products round 5 times
+//    (<= 6.4 u), the final subtraction rounds a value below 2.3 (<= 2.3 u),
+//    and the kernel's a + eps / a - eps round once more (<= 2.6 u):
+//    < 12 u < 2^-20; f64 steps and the underflow terms bounded at
+//    PF_NORM_MIN are far below the remaining 4 u.
+// eps = 1.01 (rho + acc) + 2^-20, acc = (d + 8) u (1.001 + 2.012 sqrt(d)
+// maxabs / norm), evaluated in f64 and rounded UP to f32.
+__host__ __device__ static inline void pf_i8_row(
+    const float *x, uint64_t xstride, uint32_t d, double norm, uint8_t *codes,
+    uint64_t cstride, float *scale, float *pscale, float *eps) {
+	float m = 0.f;
+	bool bad = false;
+	for (uint32_t k = 0; k < d; k++) {
+		const float v = x[(uint64_t)k * xstride];
+		if ((__builtin_bit_cast(uint32_t, v) & 0x7F800000u) == 0x7F800000u)
+			bad = true;
+		m = fmaxf(m, fabsf(v));
+	}
+	if (bad || !(norm >= PF_NORM_MIN && norm <= PF_NORM_MAX) || !(m > 0.f)) {
+		for (uint32_t k = 0; k < d; k++)
+			codes[(uint64_t)k * cstride] = 128;
+		*scale = *pscale = __builtin_bit_cast(float, 0x7FC00000u);
+		*eps = 0.f;
+		return;
+	}
+	const float sc = (float)((double)m / 127.0);
+	const double sd = (double)sc;
+	double res2 = 0.0;
+	for (uint32_t k = 0; k < d; k++) {
+		const double xv = (double)x[(uint64_t)k * xstride];
+		double c = rint(xv / sd);
+		c = c > 127.0 ? 127.0 : (c < -127.0 ? -127.0 : c);
+		const double r = xv - sd * c;
+		res2 += r * r;
+		codes[(uint64_t)k * cstride] = (uint8_t)((int)c + 128);
+	}
+	const double rho = sqrt(res2) / norm * (1.0 + 0x1p-40);
+	const double acc = (double)(d + 8) * 0x1p-24 *
+	                   (1.001 + 2.012 * sqrt((double)d) * ((double)m / norm));
+	const double e = 1.01 * (rho + acc) + 0x1p-20;
+	float ef = (float)e;
+	if ((double)ef < e) // round up: e is positive and finite
+		ef = __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, ef) + 1u);
+	*scale = sc;
+	*pscale = (float)(sd / norm);
+	*eps = ef;
+}
+
+// Build the int8 shadow: one lane per row (coalesced f32 reads across the
+// wave, two passes over the row: maxabs, then codes and residual).
+__global__ void k_shadow_i8(const float *__restrict__ cm,
+                            const double *__restrict__ norms,
+                            uint8_t *__restrict__ sh,
+                            float *__restrict__ pscale,
+                            float *__restrict__ peps, uint64_t n,
+                            uint64_t n_pad, uint64_t sn_pad, uint32_t d) {
+	const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (r >= sn_pad)
+		return;
+	float sc, ps = __uint_as_float(0x7FC00000u), pe = 0.f;
+	if (r < n) {
+		pf_i8_row(cm + r, n_pad, d, norms[r], sh + r, sn_pad, &sc, &ps, &pe);
+	} else { // padding row: never covered
+		for (uint32_t k = 0; k < d; k++)
+			sh[(uint64_t)k * sn_pad + r] = 128;
+	}
+	pscale[r] = ps;
+	peps[r] = pe;
+}
+
+// k_prefilter over the int8 shadow: 16 rows per lane from one 16-byte load
+// per feature, 8 loads in flight, one convert and one FMA per element.
+// a_i = 1 - (t_i - qbias) * inv_q * pscale_i. The block top-K and the merge
+// run on the UPPER bounds u_i = a_i + peps_i; scores[] receives the LOWER
+// bounds l_i = a_i - peps_i (uncovered rows and non-finite scores -inf, kept
+// out of the top-K, as in k_prefilter). k_pf_compact then passes every row
+// with l_i <= U_K, the Kth smallest upper bound: the K covered rows with
+// u_i <= U_K have exact distances <= U_K, so the exact Kth distance D_K <=
+// U_K, and a true top-K row, ties included, has l_i <= d_i <= D_K <= U_K.
+// The 4096-row tile feeds the select in two 2048-row halves through the
+// same 17 KB buffer k_prefilter uses.
+__global__ __launch_bounds__(THREADS) void k_prefilter_i8(
+    const uint8_t *__restrict__ sh, const float *__restrict__ pscale,
+    const float *__restrict__ peps, uint64_t n, uint64_t sn_pad, uint32_t d,
+    const float *__restrict__ qg, float inv_qnorm, float qbias, uint32_t k,
+    uint64_t rows_per_block, float *__restrict__ scores,
+    Cand *__restrict__ block_out, uint32_t *__restrict__ cand_cnt) {
+	__shared__ uint64_t buf[PF_TILE + MAX_K];
+	__shared__ uint64_t topk[MAX_K];
+	__shared__ int cnt;
+	__shared__ int topk_n;
+	__shared__ uint64_t kth;
+
+	if (threadIdx.x == 0) {
+		cnt = 0;
+		topk_n = 0;
+		kth = ~0ULL;
+		if (blockIdx.x == 0)
+			*cand_cnt = 0;
+	}
+	__syncthreads();
+
+	uint64_t row_begin = (uint64_t)blockIdx.x * rows_per_block;
+	uint64_t row_end = row_begin + rows_per_block;
+	if (row_end > n)
+		row_end = n;
+	const float ninf = __uint_as_float(0xFF800000u);
+
+	for (uint64_t tile_base = row_begin; tile_base < row_end;
+	     tile_base += PF8_TILE) {
+		const uint64_t r0 =
+		    tile_base + (uint64_t)threadIdx.x * PF8_ROWS_PER_LANE;
+		const uint8_t *p = sh + r0;
+		float acc[16];
+#pragma unroll
+		for (int c = 0; c < 16; c++)
+			acc[c] = 0.f;
+#define PF8_ACC4(W, qk, o)                                                     \
+	acc[o + 0] = __fmaf_rn((float)((W) & 0xFFu), qk, acc[o + 0]);              \
+	acc[o + 1] = __fmaf_rn((float)(((W) >> 8) & 0xFFu), qk, acc[o + 1]);       \
+	acc[o + 2] = __fmaf_rn((float)(((W) >> 16) & 0xFFu), qk, acc[o + 2]);      \
+	acc[o + 3] = __fmaf_rn((float)((W) >> 24), qk, acc[o + 3]);
+#define PF8_ACC(V, qk)                                                         \
+	PF8_ACC4((V).x, qk, 0)                                                     \
+	PF8_ACC4((V).y, qk, 4)                                                     \
+	PF8_ACC4((V).z, qk, 8)                                                     \
+	PF8_ACC4((V).w, qk, 12)
+		uint32_t kk = 0;
+		for (; kk + 8 <= d; kk += 8) {
+			uint4 w[8];
+#pragma unroll
+			for (uint32_t j = 0; j < 8; j++)
+				w[j] = *(const uint4 *)(p + (uint64_t)(kk + j) * sn_pad);
+#pragma unroll
+			for (uint32_t j = 0; j < 8; j++) {
+				const float qk = qg[kk + j]; // uniform: scalar load
+				PF8_ACC(w[j], qk)
+			}
+		}
+		for (; kk < d; kk++) {
+			const uint4 w1 = *(const uint4 *)(p + (uint64_t)kk * sn_pad);
+			const float qk = qg[kk];
+			PF8_ACC(w1, qk)
+		}
+#undef PF8_ACC
+#undef PF8_ACC4
+		float up[16];
+		bool ok[16];
+#pragma unroll
+		for (int g = 0; g < 4; g++) {
+			const float4 s4 = *(const float4 *)(pscale + r0 + 4 * g);
+			const float4 e4 = *(const float4 *)(peps + r0 + 4 * g);
+			const float ps[4] = {s4.x, s4.y, s4.z, s4.w};
+			const float pe[4] = {e4.x, e4.y, e4.z, e4.w};
+			float lo[4];
+#pragma unroll
+			for (int j = 0; j < 4; j++) {
+				const int c = 4 * g + j;
+				const float a =
+				    1.0f - (acc[c] - qbias) * inv_qnorm * ps[j];
+				ok[c] = (r0 + c) < row_end &&
+				        (__float_as_uint(a) & 0x7F800000u) != 0x7F800000u;
+				up[c] = ok[c] ? a + pe[j] : ninf;
+				lo[j] = ok[c] ? a - pe[j] : ninf;
+			}
+			*(float4 *)(scores + r0 + 4 * g) =
+			    make_float4(lo[0], lo[1], lo[2], lo[3]);
+		}
+
+		// threshold check + candidate append, one 2048-row half at a time
+#pragma unroll
+		for (int h = 0; h < 2; h++) {
+			const uint64_t kthv = kth;
+			const int full = (topk_n >= (int)k);
+#pragma unroll
+			for (int c8 = 0; c8 < 8; c8++) {
+				const int c = 8 * h + c8;
+				if (!ok[c])
+					continue;
+				uint64_t v =
+				    ((uint64_t)d_key32(up[c]) << 32) | (uint32_t)(r0 + c);
+				if (!full || v < kthv) {
+					int idx = atomicAdd(&cnt, 1);
+					buf[idx] = v;
+				}
+			}
+			__syncthreads();
+
+			if (cnt > 0) {
+				int m = cnt;
+				for (int i = threadIdx.x; i < topk_n; i += THREADS)
+					buf[m + i] = topk[i];
+				int total = m + topk_n;
+				__syncthreads();
+				int new_n;
+				pf_block_select(buf, total, topk, (int)k, &new_n);
+				if (threadIdx.x == 0) {
+					topk_n = new_n;
+					if (new_n >= (int)k)
+						kth = topk[k - 1];
+					cnt = 0;
+				}
+			}
+			__syncthreads();
+		}
+	}
+
+	// block winners as Cand{upper bound, row} (pad with +inf) for k_merge
+	if (threadIdx.x < k) {
+		Cand c;
+		if ((int)threadIdx.x < topk_n) {
+			c.dist = (double)d_unkey32((uint32_t)(topk[threadIdx.x] >> 32));
+			c.id = (uint32_t)topk[threadIdx.x];
+		} else {
+			c.dist = __longlong_as_double(0x7FF0000000000000LL); // +inf
+			c.id = ~0ULL;
+		}
+		block_out[(uint64_t)blockIdx.x * k + threadIdx.x] = c;
+	}
+}
+
+// One pass over scores[]: append every row with score <= T_K + 2 eps to the
+// candidate list. bf16 tier: scores are a_i, approx_top[k-1].dist is A_K and
+// eps = pf_eps(d). int8 tier: scores are the lower bounds l_i,
+// approx_top[k-1].dist is U_K and eps = 0. T_K is +inf when fewer than K
+// rows carry a bound: then every row passes. The counter keeps counting past
 // PF_CAND_CAP; the list is never written past it.
 __global__ void k_pf_compact(const float *__restrict__ scores, uint64_t n,
                              const Cand *__restrict__ approx_top, uint32_t k,
@@ -2210,6 +2485,10 @@ static void free_table(Table &t) {
 		(void)hipFree(t.shadow);
 	if (t.pinv)
 		(void)hipFree(t.pinv);
+	if (t.shadow8)
+		(void)hipFree(t.shadow8);
+	if (t.pscale)
+		(void)hipFree(t.pscale); // peps lives in the same allocation
 	t = Table{};
 }
 
@@ -2329,8 +2608,15 @@ static void free_shadow(sdbv_ctx *ctx, Table *t) {
 		(void)hipFree(t->shadow);
 	if (t->pinv)
 		(void)hipFree(t->pinv);
+	if (t->shadow8)
+		(void)hipFree(t->shadow8);
+	if (t->pscale)
+		(void)hipFree(t->pscale);
 	t->shadow = nullptr;
 	t->pinv = nullptr;
+	t->shadow8 = nullptr;
+	t->pscale = nullptr;
+	t->peps = nullptr;
 	t->bytes -= t->shadow_bytes;
 	t->shadow_bytes = 0;
 	t->sn_pad = 0;
@@ -2345,6 +2631,8 @@ static int build_shadow(sdbv_ctx *ctx, Table *t) {
 		return SDBV_ERR_UNSUPPORTED;
 	if (t->shadow)
 		return SDBV_OK;
+	if (t->shadow8)
+		free_shadow(ctx, t);
 	uint64_t sn_pad = ((t->n + PF_TILE - 1) / PF_TILE) * PF_TILE;
 	if (sn_pad == 0)
 		sn_pad = PF_TILE;
@@ -2372,6 +2660,41 @@ static int build_shadow(sdbv_ctx *ctx, Table *t) {
 	return SDBV_OK;
 }
 
+// The int8 shadow instead: d + 8 bytes per row (+25 %). Same contract.
+static int build_shadow_i8(sdbv_ctx *ctx, Table *t) {
+	if (t->metric != SDBV_METRIC_COSINE)
+		return SDBV_ERR_UNSUPPORTED;
+	if (t->shadow8)
+		return SDBV_OK;
+	if (t->shadow)
+		free_shadow(ctx, t);
+	uint64_t sn_pad = ((t->n + PF8_TILE - 1) / PF8_TILE) * PF8_TILE;
+	if (sn_pad == 0)
+		sn_pad = PF8_TILE;
+	uint64_t sh_bytes = (uint64_t)t->d * sn_pad;
+	uint64_t side_bytes = 2 * sn_pad * sizeof(float);
+	if (hipMalloc(&t->shadow8, sh_bytes) != hipSuccess ||
+	    hipMalloc(&t->pscale, side_bytes) != hipSuccess) {
+		(void)hipGetLastError(); // allocation failure is not sticky
+		if (t->shadow8)
+			(void)hipFree(t->shadow8);
+		t->shadow8 = nullptr;
+		t->pscale = nullptr;
+		return SDBV_ERR_OOM;
+	}
+	t->peps = t->pscale + sn_pad;
+	t->sn_pad = sn_pad;
+	t->shadow_bytes = sh_bytes + side_bytes;
+	t->bytes += t->shadow_bytes;
+	hipLaunchKernelGGL(k_shadow_i8, dim3((uint32_t)(sn_pad / 256)), dim3(256),
+	                   0, ctx->stream, t->cm, t->norms, t->shadow8, t->pscale,
+	                   t->peps, t->n, t->n_pad, sn_pad, t->d);
+	HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+	HIP_CHECK(ctx, hipGetLastError());
+	refresh_bytes_staged(ctx);
+	return SDBV_OK;
+}
+
 // Default minimum row count from which scan staging builds the shadow: the
 // measured crossover (profiles/prefilter_scan.md) below which the extra
 // launches of the prefilter path cost more than the halved stream saves.
@@ -2387,6 +2710,26 @@ static bool shadow_policy(const Table *t) {
 		return false;
 	uint64_t min_rows = PF_DEFAULT_MIN_ROWS;
 	const char *m = getenv("SDBV_SCAN_PREFILTER_MIN_ROWS");
+	if (m && *m)
+		min_rows = strtoull(m, nullptr, 10);
+	return t->n >= min_rows;
+}
+
+// Default minimum row count from which the shadow that staging builds is the
+// int8 one: the measured crossover against the bf16 tier
+// (profiles/prefilter_i8.md); never below PF_DEFAULT_MIN_ROWS.
+#define PF8_DEFAULT_MIN_ROWS 500000ull
+
+// Which shadow staging builds once shadow_policy asked for one:
+// SDBV_SCAN_PREFILTER_I8=0 keeps bf16; SDBV_SCAN_PREFILTER_I8_MIN_ROWS
+// overrides the int8 minimum row count (independent of
+// SDBV_SCAN_PREFILTER_MIN_ROWS).
+static bool shadow_policy_i8(const Table *t) {
+	const char *e = getenv("SDBV_SCAN_PREFILTER_I8");
+	if (e && e[0] == '0' && e[1] == 0)
+		return false;
+	uint64_t min_rows = PF8_DEFAULT_MIN_ROWS;
+	const char *m = getenv("SDBV_SCAN_PREFILTER_I8_MIN_ROWS");
 	if (m && *m)
 		min_rows = strtoull(m, nullptr, 10);
 	return t->n >= min_rows;
@@ -2413,7 +2756,8 @@ static int finish_stage(sdbv_ctx *ctx, Table *t, bool scan_table) {
 	// a table staged for scanning gets the prefilter shadow when the policy
 	// asks for one; without the memory for it the table simply has none
 	if (scan_table && shadow_policy(t)) {
-		int rc = build_shadow(ctx, t);
+		int rc = shadow_policy_i8(t) ? build_shadow_i8(ctx, t)
+		                             : build_shadow(ctx, t);
 		if (rc != SDBV_OK && rc != SDBV_ERR_OOM)
 			return rc;
 	}
@@ -2473,12 +2817,36 @@ int sdbv_table_set_prefilter(sdbv_ctx *ctx, uint64_t table, int on) {
 		return SDBV_ERR_UNSUPPORTED;
 	if (on)
 		return build_shadow(ctx, t);
-	if (t->shadow)
+	if (t->shadow || t->shadow8)
 		free_shadow(ctx, t);
 	return SDBV_OK;
 }
 
+int sdbv_table_set_prefilter_kind(sdbv_ctx *ctx, uint64_t table, int kind) {
+	if (kind < 0 || kind > 2)
+		return SDBV_ERR_BAD_ARG;
+	if (kind < 2)
+		return sdbv_table_set_prefilter(ctx, table, kind);
+	std::lock_guard<std::mutex> lk(ctx->mu);
+	auto it = ctx->tables.find(table);
+	if (it == ctx->tables.end())
+		return SDBV_ERR_NO_TABLE;
+	return build_shadow_i8(ctx, &it->second);
+}
+
 float sdbv_prefilter_eps(uint32_t d) { return pf_eps(d); }
+
+int sdbv_prefilter_i8_row(const float *x, uint32_t d, double norm,
+                          int8_t *codes, float *scale, float *eps) {
+	if (!x || !codes || !scale || !eps || d == 0 || d > MAX_D)
+		return SDBV_ERR_BAD_ARG;
+	uint8_t stored[MAX_D];
+	float pscale;
+	pf_i8_row(x, 1, d, norm, stored, 1, scale, &pscale, eps);
+	for (uint32_t k = 0; k < d; k++)
+		codes[k] = (int8_t)((int)stored[k] - 128);
+	return SDBV_OK;
+}
 
 float sdbv_bf16_rne(float x) {
 	uint32_t u;
@@ -2658,27 +3026,32 @@ static int knn_large_k(sdbv_ctx *ctx, Table &t, const float *q, uint32_t d,
 // block the same span). A grid of a few more blocks than the chip holds runs
 // a second, mostly empty round with too few bytes in flight per CU — 3.5 %
 // of the kernel at 10M rows (profiles/prefilter_scan.md).
-static uint64_t prefilter_grid(sdbv_ctx *ctx, uint64_t n,
+static uint64_t prefilter_grid(sdbv_ctx *ctx, uint64_t n, bool i8,
                                uint64_t *rows_per_block) {
-	if (ctx->pf_slots == 0) {
+	uint64_t &slots = i8 ? ctx->pf8_slots : ctx->pf_slots;
+	if (slots == 0) {
 		int per_cu = 0, cus = 0;
-		if (hipOccupancyMaxActiveBlocksPerMultiprocessor(
-		        &per_cu, k_prefilter, THREADS, 0) != hipSuccess ||
+		hipError_t e = i8 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(
+		                        &per_cu, k_prefilter_i8, THREADS, 0)
+		                  : hipOccupancyMaxActiveBlocksPerMultiprocessor(
+		                        &per_cu, k_prefilter, THREADS, 0);
+		if (e != hipSuccess ||
 		    hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount,
 		                          ctx->device) != hipSuccess ||
 		    per_cu <= 0 || cus <= 0) {
 			(void)hipGetLastError();
-			ctx->pf_slots = 2048;
+			slots = 2048;
 		} else {
-			ctx->pf_slots = (uint64_t)per_cu * (uint64_t)cus;
+			slots = (uint64_t)per_cu * (uint64_t)cus;
 		}
 	}
-	uint64_t tiles = (n + PF_TILE - 1) / PF_TILE;
-	uint64_t nblocks = tiles < ctx->pf_slots ? tiles : ctx->pf_slots;
+	const uint64_t tile = i8 ? PF8_TILE : PF_TILE;
+	uint64_t tiles = (n + tile - 1) / tile;
+	uint64_t nblocks = tiles < slots ? tiles : slots;
 	if (nblocks == 0)
 		nblocks = 1;
 	uint64_t tiles_per_block = (tiles + nblocks - 1) / nblocks;
-	*rows_per_block = tiles_per_block * PF_TILE;
+	*rows_per_block = tiles_per_block * tile;
 	return (n + *rows_per_block - 1) / *rows_per_block;
 }
 
@@ -2689,7 +3062,8 @@ static uint64_t prefilter_grid(sdbv_ctx *ctx, uint64_t n,
 // list overflowed and host_out is void: the caller runs the exact scan.
 // One D2H copy and one sync, like the exact path. Caller holds ctx->mu.
 static int knn_prefilter(sdbv_ctx *ctx, Table &t, uint32_t k, double q_norm,
-                         Cand *host_out, uint32_t *ncand) {
+                         float qbias, Cand *host_out, uint32_t *ncand) {
+	const bool i8 = t.shadow8 != nullptr;
 	if (ctx->pf_scores_cap < t.sn_pad) {
 		if (ctx->pf_scores)
 			(void)hipFree(ctx->pf_scores);
@@ -2707,7 +3081,7 @@ static int knn_prefilter(sdbv_ctx *ctx, Table &t, uint32_t k, double q_norm,
 		HIP_CHECK(ctx, hipMalloc(&ctx->pf_res, (MAX_K + 2) * sizeof(Cand)));
 
 	uint64_t rows_per_block = 0;
-	uint64_t nblocks = prefilter_grid(ctx, t.n, &rows_per_block);
+	uint64_t nblocks = prefilter_grid(ctx, t.n, i8, &rows_per_block);
 	Cand *res = (Cand *)ctx->pf_res;
 	// device counter: behind the k results and the copy of the count that
 	// k_pf_final appends to them
@@ -2715,13 +3089,21 @@ static int knn_prefilter(sdbv_ctx *ctx, Table &t, uint32_t k, double q_norm,
 	const float inv_q = (float)(1.0 / q_norm);
 
 	HIP_CHECK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-	hipLaunchKernelGGL(k_prefilter, dim3((uint32_t)nblocks), dim3(THREADS), 0,
-	                   ctx->stream, t.shadow, t.pinv, t.n, t.sn_pad, t.d,
-	                   ctx->q_dev, inv_q, k, rows_per_block, ctx->pf_scores,
-	                   (Cand *)ctx->block_out, cand_cnt);
+	if (i8)
+		hipLaunchKernelGGL(k_prefilter_i8, dim3((uint32_t)nblocks),
+		                   dim3(THREADS), 0, ctx->stream, t.shadow8, t.pscale,
+		                   t.peps, t.n, t.sn_pad, t.d, ctx->q_dev, inv_q, qbias,
+		                   k, rows_per_block, ctx->pf_scores,
+		                   (Cand *)ctx->block_out, cand_cnt);
+	else
+		hipLaunchKernelGGL(k_prefilter, dim3((uint32_t)nblocks), dim3(THREADS),
+		                   0, ctx->stream, t.shadow, t.pinv, t.n, t.sn_pad,
+		                   t.d, ctx->q_dev, inv_q, k, rows_per_block,
+		                   ctx->pf_scores, (Cand *)ctx->block_out, cand_cnt);
 	HIP_CHECK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
 	{
-		// K smallest approximate distances -> final_out (A_K = entry k-1)
+		// K smallest approximate distances (int8: upper bounds) ->
+		// final_out (A_K, or U_K, = entry k-1)
 		uint64_t total = nblocks * k;
 		const uint64_t G = 32;
 		if (total > 4096 && nblocks > G) {
@@ -2748,8 +3130,8 @@ static int knn_prefilter(sdbv_ctx *ctx, Table &t, uint32_t k, double q_norm,
 			nb = 1;
 		hipLaunchKernelGGL(k_pf_compact, dim3((uint32_t)nb), dim3(THREADS), 0,
 		                   ctx->stream, ctx->pf_scores, t.n,
-		                   (const Cand *)ctx->final_out, k, pf_eps(t.d),
-		                   cand_cnt, ctx->pf_rows);
+		                   (const Cand *)ctx->final_out, k,
+		                   i8 ? 0.0f : pf_eps(t.d), cand_cnt, ctx->pf_rows);
 		hipLaunchKernelGGL(k_pf_rescore, dim3(PF_RESCORE_BLOCKS), dim3(64), 0,
 		                   ctx->stream, t.cm, t.norms, t.ids_dev, t.n_pad,
 		                   t.d, ctx->q_dev, q_norm, cand_cnt, ctx->pf_rows,
@@ -2855,8 +3237,9 @@ int sdbv_knn_bruteforce(sdbv_ctx *ctx, uint64_t table, const float *q,
 	nblocks = (t.n + rows_per_block - 1) / rows_per_block;
 
 	uint64_t pf_rows_per_block = 0;
-	uint64_t scratch_blocks =
-	    std::max(nblocks, prefilter_grid(ctx, t.n, &pf_rows_per_block));
+	uint64_t scratch_blocks = std::max(
+	    nblocks,
+	    prefilter_grid(ctx, t.n, t.shadow8 != nullptr, &pf_rows_per_block));
 	int rc = ensure_query_scratch(ctx, d, scratch_blocks, k);
 	if (rc != SDBV_OK)
 		return rc;
@@ -2871,15 +3254,23 @@ int sdbv_knn_bruteforce(sdbv_ctx *ctx, uint64_t table, const float *q,
 	// the window the bound is proven for (a non-finite element makes the
 	// norm non-finite). Everything else, and a query whose candidate list
 	// overflowed, takes the exact scan; results never depend on the choice.
-	if (t.shadow && q_norm >= PF_NORM_MIN && q_norm <= PF_NORM_MAX) {
+	if ((t.shadow || t.shadow8) && q_norm >= PF_NORM_MIN &&
+	    q_norm <= PF_NORM_MAX) {
+		// int8 tier: the bias term 128 * sum q_k, one f64 sum rounded once
+		double qsum = 0.0;
+		if (t.shadow8)
+			for (uint32_t i = 0; i < d; i++)
+				qsum += (double)q[i];
 		uint32_t ncand = 0;
-		rc = knn_prefilter(ctx, t, k, q_norm, host_out, &ncand);
+		rc = knn_prefilter(ctx, t, k, q_norm, (float)(128.0 * qsum), host_out,
+		                   &ncand);
 		if (rc != SDBV_OK)
 			return rc;
 		ctx->stats.last_prefilter_candidates = ncand;
-		ctx->stats.last_scan_path = ncand <= PF_CAND_CAP ? 1 : 2;
+		ctx->stats.last_scan_path = (ncand <= PF_CAND_CAP ? 1u : 2u) +
+		                            (t.shadow8 ? 2u : 0u);
 	}
-	if (ctx->stats.last_scan_path != 1) {
+	if (ctx->stats.last_scan_path != 1 && ctx->stats.last_scan_path != 3) {
 		rc = knn_exact_scan(ctx, t, k, q_norm, nblocks, rows_per_block,
 		                    host_out);
 		if (rc != SDBV_OK)
