@@ -91,7 +91,9 @@ typedef struct sdbv_stats {
 	uint32_t last_scan_path; /* sdbv_knn_bruteforce: 0 = exact scan, 1 = bf16
 	                            prefilter, 2 = bf16 prefilter overflowed, then
 	                            exact scan, 3 = int8 prefilter, 4 = int8
-	                            prefilter overflowed, then exact scan */
+	                            prefilter overflowed, then exact scan, 5 = int6
+	                            prefilter, 6 = int6 prefilter overflowed, then
+	                            exact scan */
 } sdbv_stats;
 
 /* Create a context on HIP device `device` (-1 = current device). */
@@ -118,7 +120,12 @@ int sdbv_get_stats(sdbv_ctx *, sdbv_stats *out);
  * per row more (+25 %), if the table also has at least
  * SDBV_SCAN_PREFILTER_I8_MIN_ROWS rows (environment, default 500000,
  * independent of the first threshold) and SDBV_SCAN_PREFILTER_I8 is not 0;
- * otherwise the bf16 one, d*2 + 4 B per row more (+50 %). A table holds at
+ * otherwise the bf16 one, d*2 + 4 B per row more (+50 %). An int8-eligible
+ * table gets the int6 shadow instead, 0.75 * d_pad + 12 B per row (d_pad = d
+ * rounded up to a multiple of 32), if it also has at least
+ * SDBV_SCAN_PREFILTER_I6_MIN_ROWS rows (environment, default 500000,
+ * independent of the other thresholds) and SDBV_SCAN_PREFILTER_I6 is not 0.
+ * A table holds at
  * most one shadow. The shadow never changes a result (see
  * sdbv_knn_bruteforce). Tables staged for graph search (sdbv_hnsw_finalize,
  * sdbv_index_*) never get one. */
@@ -143,8 +150,15 @@ int sdbv_stage_synthetic(sdbv_ctx *, uint64_t table, uint64_t n, uint32_t d,
 int sdbv_table_set_prefilter(sdbv_ctx *, uint64_t table, int on);
 /* The same with the kind spelled out: 0 = none, 1 = bf16, 2 = int8 (codes in
  * [-127, 127] with one f32 scale per row, plus the row's own proven error
- * bound: d + 8 B per row). Setting a kind frees a shadow of the other kind. */
+ * bound: d + 8 B per row). Setting a kind frees a shadow of another kind;
+ * any other value is SDBV_ERR_BAD_ARG. */
 int sdbv_table_set_prefilter_kind(sdbv_ctx *, uint64_t table, int kind);
+/* Give the table the int6 shadow (codes in [-31, 31], one f32 scale, the
+ * row's bound and the sum of its stored codes: 0.75 * d_pad + 12 B per row),
+ * freeing a shadow of another kind. Errors as for
+ * sdbv_table_set_prefilter; free it with sdbv_table_set_prefilter(.., 0) or
+ * sdbv_table_set_prefilter_kind(.., 0). */
+int sdbv_table_set_prefilter_i6(sdbv_ctx *, uint64_t table);
 /* Host-only: the proven bound on |exact - prefilter| cosine distance at
  * dimension d, and f32 -> bf16 round-to-nearest-even (returned as f32) as
  * the shadow is built. */
@@ -160,6 +174,26 @@ float sdbv_bf16_rne(float x);
  * prefilter always recomputes such a row. */
 int sdbv_prefilter_i8_row(const float *x, uint32_t d, double norm,
                           int8_t *codes, float *scale, float *eps);
+/* Host-only: the same for the int6 shadow. codes[k] = rint(x[k] / scale) in
+ * [-31, 31], *scale = f32(maxabs / 31), *xsum = sum of the stored codes
+ * (codes[k] + 32) over the row padded with zero codes to a multiple of 32
+ * features, *eps = the proven bound of THIS row against an exactly
+ * represented query; for a query with residual rho_q (sdbv_prefilter_q12)
+ * the prefilter uses e = eps + (1 + eps) * qeps in f32, qeps = 1.01 * rho_q
+ * rounded up to f32. Uncovered rows as for int8. */
+int sdbv_prefilter_i6_row(const float *x, uint32_t d, double norm,
+                          int8_t *codes, float *scale, float *eps,
+                          uint32_t *xsum);
+/* Host-only: quantise one query of d <= 4096 f32 elements for the int6 tier
+ * exactly as sdbv_knn_bruteforce does. codes[k] = rint(q[k] / sq) in
+ * [-2047, 2047], *sq = f32(maxabs / 2047), *rho_q = |q - sq * codes| / |q|
+ * (|q| = sqrt of the restated f32 sum-of-squares chain) computed in f64 and
+ * rounded up to f32, *qs = sum of (codes[k] + 2048) over the query padded
+ * with zero codes to a multiple of 32 features. A query the prefilter never
+ * runs for (non-finite, norm outside [2^-30, 2^30]) gets zero codes,
+ * *sq = NaN and *rho_q = 0. */
+int sdbv_prefilter_q12(const float *q, uint32_t d, int16_t *codes, float *sq,
+                       float *rho_q, uint32_t *qs);
 
 uint64_t sdbv_table_rows(sdbv_ctx *, uint64_t table);
 int sdbv_drop_table(sdbv_ctx *, uint64_t table);
@@ -188,7 +222,9 @@ void sdbv_gen_f32(uint64_t seed, uint64_t row0, uint64_t nrows, uint32_t d,
  * bound sdbv_prefilter_eps(d) of the Kth approximate distance; or int8 (a
  * quarter), keeping every row whose approximate distance minus its own
  * proven bound does not exceed the Kth smallest approximate distance plus
- * bound. It recomputes those rows with the exact chain. Exactness guarantee: ids and distance bits equal the exact scan's
+ * bound; or int6 (0.75 of int8), the same rule on an exact integer dot
+ * product of 6-bit row codes and a 12-bit quantised query, whose own
+ * quantisation error is part of each row's bound. It recomputes those rows with the exact chain. Exactness guarantee: ids and distance bits equal the exact scan's
  * for every input — rows the bound cannot cover are always recomputed, and
  * a query with more than 16384 candidates reruns the exact scan
  * (sdbv_stats.last_scan_path tells which path ran). */

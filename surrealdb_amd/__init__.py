@@ -89,9 +89,16 @@ def lib():
     L.sdbv_drop_table.argtypes = [vp, u64]
     L.sdbv_table_set_prefilter.argtypes = [vp, u64, ctypes.c_int]
     L.sdbv_table_set_prefilter_kind.argtypes = [vp, u64, ctypes.c_int]
+    L.sdbv_table_set_prefilter_i6.argtypes = [vp, u64]
     L.sdbv_prefilter_i8_row.argtypes = [f32p, u32, ctypes.c_double,
                                         ctypes.POINTER(ctypes.c_int8), f32p,
                                         f32p]
+    L.sdbv_prefilter_i6_row.argtypes = [f32p, u32, ctypes.c_double,
+                                        ctypes.POINTER(ctypes.c_int8), f32p,
+                                        f32p, ctypes.POINTER(ctypes.c_uint32)]
+    L.sdbv_prefilter_q12.argtypes = [f32p, u32,
+                                     ctypes.POINTER(ctypes.c_int16), f32p,
+                                     f32p, ctypes.POINTER(ctypes.c_uint32)]
     L.sdbv_prefilter_eps.restype = ctypes.c_float
     L.sdbv_prefilter_eps.argtypes = [u32]
     L.sdbv_bf16_rne.restype = ctypes.c_float
@@ -258,6 +265,12 @@ class Context:
         _check(self._ptr, lib().sdbv_table_set_prefilter_kind(
             self._ptr, table, int(kind)), "sdbv_table_set_prefilter_kind")
 
+    def table_set_prefilter_i6(self, table):
+        """Give the table the int6 prefilter shadow, freeing a shadow of
+        another kind (free it with table_set_prefilter_kind(table, 0))."""
+        _check(self._ptr, lib().sdbv_table_set_prefilter_i6(
+            self._ptr, table), "sdbv_table_set_prefilter_i6")
+
     def knn_bruteforce(self, table, q, k):
         import numpy as np
         q = np.ascontiguousarray(q, dtype=np.float32)
@@ -344,6 +357,46 @@ def prefilter_i8_row(x, norm):
         codes.ctypes.data_as(ctypes.POINTER(ctypes.c_int8)),
         ctypes.byref(scale), ctypes.byref(eps)), "sdbv_prefilter_i8_row")
     return codes, np.float32(scale.value), np.float32(eps.value)
+
+
+def prefilter_i6_row(x, norm):
+    """Quantise one f32 row for the int6 prefilter shadow as staging does
+    (host-only): (codes int8[d] in [-31, 31], scale f32, eps f32, xsum).
+    xsum is the sum of the stored codes (code + 32) over the row padded to a
+    multiple of 32 features; scale is NaN for a row the bound cannot
+    cover."""
+    import numpy as np
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    codes = np.empty(x.size, dtype=np.int8)
+    scale = ctypes.c_float(0.0)
+    eps = ctypes.c_float(0.0)
+    xsum = ctypes.c_uint32(0)
+    _check(None, lib().sdbv_prefilter_i6_row(
+        x.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), x.size, float(norm),
+        codes.ctypes.data_as(ctypes.POINTER(ctypes.c_int8)),
+        ctypes.byref(scale), ctypes.byref(eps), ctypes.byref(xsum)),
+        "sdbv_prefilter_i6_row")
+    return codes, np.float32(scale.value), np.float32(eps.value), xsum.value
+
+
+def prefilter_q12(q):
+    """Quantise one f32 query for the int6 prefilter as a search call does
+    (host-only): (codes int16[d] in [-2047, 2047], sq f32, rho_q f32, Qs).
+    rho_q is the query's relative residual rounded up; Qs the sum of
+    code + 2048 over the query padded to a multiple of 32 features; sq is
+    NaN for a query the prefilter never runs for."""
+    import numpy as np
+    q = np.ascontiguousarray(q, dtype=np.float32)
+    codes = np.empty(q.size, dtype=np.int16)
+    sq = ctypes.c_float(0.0)
+    rho = ctypes.c_float(0.0)
+    qs = ctypes.c_uint32(0)
+    _check(None, lib().sdbv_prefilter_q12(
+        q.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), q.size,
+        codes.ctypes.data_as(ctypes.POINTER(ctypes.c_int16)),
+        ctypes.byref(sq), ctypes.byref(rho), ctypes.byref(qs)),
+        "sdbv_prefilter_q12")
+    return codes, np.float32(sq.value), np.float32(rho.value), qs.value
 
 
 def bf16_rne(x):

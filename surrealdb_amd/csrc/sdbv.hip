@@ -101,6 +101,14 @@ struct Table {
 	uint8_t *shadow8 = nullptr;
 	float *pscale = nullptr;
 	float *peps = nullptr;
+	// or the int6 shadow: 6-bit codes, bias 32, lane = row, features in
+	// groups of 32; plane H [G][sn_pad][4 dwords] holds the high nibbles,
+	// plane L [G][sn_pad][2 dwords] the low pairs (one allocation, L behind
+	// H); pscale, peps and xsum (the row's sum of stored codes) share the
+	// side allocation
+	uint32_t *shadow6 = nullptr;
+	uint32_t *shadow6l = nullptr;
+	uint32_t *xsum = nullptr;
 	uint64_t sn_pad = 0;
 	uint64_t shadow_bytes = 0;
 	uint64_t bytes = 0;
@@ -130,6 +138,7 @@ struct sdbv_ctx {
 	void *pf_res = nullptr;      // [MAX_K + 2] Cand: top-k, the count, counter
 	uint64_t pf_slots = 0;       // k_prefilter blocks the device holds at once
 	uint64_t pf8_slots = 0;      // the same for k_prefilter_i8
+	uint64_t pf6_slots = 0;      // the same for k_prefilter_i6
 	// batched path
 	rocblas_handle blas = nullptr;
 	float *S = nullptr; // chunk scores scratch, [chunk][b] col-major
@@ -1125,9 +1134,369 @@ __global__ __launch_bounds__(THREADS) void k_prefilter_i8(
 	}
 }
 
+// ---------------------------------------------------------------------------
+// Int6 tier of the prefilter: 0.75 of the int8 tier's bytes. Row r is stored
+// as symmetric codes c_k in [-31, 31] with one f32 scale_r = maxabs_r / 31,
+// as bias-32 codes xu_k = c_k + 32 in [1, 63], split into a high nibble
+// xu >> 2 and a low pair xu & 3. The query is quantised on the host to
+// cq_k in [-2047, 2047], bias 2048, three nibbles per element. The dot
+// product runs in integers on v_dot8_u32_u4 (8 four-bit pairs per
+// instruction) and is exact; the biases come off once per row.
+//
+// Layout, lane = row: features in groups of 32, G = ceil(d / 32). Plane H is
+// [G][sn_pad rows][4 dwords]: dword m holds the high nibbles of features
+// 32 g + 8 m + i in nibble i. Plane L is [G][sn_pad rows][2 dwords]: dword j
+// holds the low pairs of features 32 g + 16 j + f, f < 8 in 2-bit field 2 f
+// and f >= 8 in field 2 (f - 8) + 1, so that (w & 0x33333333) and
+// ((w >> 2) & 0x33333333) are the nibble words of features 8 (2 j) + i and
+// 8 (2 j + 1) + i: the same feature order as the H dwords, so one set of
+// query digit words serves both planes. Features past d hold xu = 32.
+// ---------------------------------------------------------------------------
+#define PF6_SWEEPS 8
+#define PF6_TILE (THREADS * PF6_SWEEPS) /* 2048 rows per select feed */
+#define PF6_QWORDS 12 /* query digit dwords per group: [3 digits][4 dwords] */
+#define PF6_UNROLL 6  /* groups in flight per lane: 9 KiB per wave */
+typedef uint32_t pf6_v4 __attribute__((ext_vector_type(4)));
+typedef uint32_t pf6_v2 __attribute__((ext_vector_type(2)));
+
+// e > 0 finite, rounded up to f32.
+__host__ __device__ static inline float pf_round_up_f32(double e) {
+	float ef = (float)e;
+	if ((double)ef < e)
+		ef = __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, ef) + 1u);
+	return ef;
+}
+
+// Quantise one row for the int6 shadow (elements x[k * xstride], k < d;
+// norm = the row's staged f64 norm) and derive its bound. The one routine
+// behind both k_shadow_i6 and sdbv_prefilter_i6_row. Writes group g's four H
+// dwords to h[g * hstride + 0..3] and its two L dwords to
+// l[g * lstride + 0..1], *scale, *pscale = f32(scale / norm), *eps and
+// *xsum = sum of the stored codes over the padded row. A row the bound
+// cannot cover (as for pf_i8_row) gets neutral codes (xu = 32), scale =
+// pscale = NaN and eps = 0: the prefilter always rescores it.
+//
+// Bound on |exact - approx| for a covered row and a query inside the norm
+// window, exact = the restated f32 chain with its f64 finish (k_scan<0>),
+// approx = 1 - f32(N) * pscale * qscale in f32 (k_prefilter_i6), where
+// N = sum c_k cq_k as an exact integer, qscale = f32(sq / |q|) and sq the
+// query's scale. In cosine units, i.e. divided by |x||q|, with u = 2^-24,
+// x^ = scale c and q^ = sq cq:
+//  - quantisation: x.q - x^.q^ = (x - x^).q + x^.(q - q^). By
+//    Cauchy-Schwarz the first term is <= rho_x |x||q| with rho_x =
+//    |x - x^| / |x|, the row's ACTUAL residual, computed here in f64 and
+//    rounded up as in pf_i8_row; the second is <= |x^| |q - q^| <=
+//    (1 + rho_x) |x| rho_q |q| with rho_q = |q - q^| / |q| the query's
+//    actual residual (pf_q12). Together rho_x + (1 + rho_x) rho_q.
+//  - exact chain: within 1.001 (d + 8) u of its exact sum, as for pf_eps.
+//  - approx chain: the integer sum adds nothing: every partial result of
+//    the digit sums and of the bias removal is below 2^32 at MAX_D
+//    (sum xu qu <= 63 * 4095 * 4096 < 2^31) and |N| <= 31 * 2047 * 4096
+//    < 2^28 fits int32.
+//  - norms: rho_x, rho_q and both chains are taken against the same computed
+//    norms, within (d + 8) u of the true ones: the factor 1.01 covers it, as
+//    for pf_eps.
+//  - finish: each element is within scale / 2 of its product, so rho_x <=
+//    sqrt(d) / 62 <= 1.04 and rho_q <= sqrt(d) / 4094 <= 0.016 at MAX_D:
+//    |approx cosine| <= (1 + rho_x)(1 + rho_q) <= 2.1. The int -> f32
+//    conversion of N, pscale, qscale and the two f32 products round 5 times
+//    (<= 10.6 u), the subtraction from 1 rounds a value below 3.1
+//    (<= 3.1 u). The kernel's e = peps + (1 + peps) qeps, qeps = 1.01 rho_q
+//    rounded up, uses peps >= rho_x for the row's residual and rounds three
+//    times on values below 2.2, 0.04 and 1.2 (<= 3.5 u), and a + e / a - e
+//    round once more on a value below 4.4 (<= 4.4 u): < 22 u < 2^-19; f64
+//    steps and the underflow terms of the exact chain bounded at
+//    PF_NORM_MIN are far below the remaining 10 u. Nothing in the approx
+//    chain can underflow: pscale >= 1 / (31 sqrt(d)), qscale >=
+//    1 / (2047 sqrt(d)).
+// eps = 1.01 (rho_x + 1.001 (d + 8) u) + 2^-19, evaluated in f64 and rounded
+// UP to f32; the query term (1 + eps) qeps is added by the kernel.
+__host__ __device__ static inline void pf_i6_row(
+    const float *x, uint64_t xstride, uint32_t d, double norm, uint32_t *h,
+    uint64_t hstride, uint32_t *l, uint64_t lstride, float *scale,
+    float *pscale, float *eps, uint32_t *xsum) {
+	const uint32_t G = (d + 31) / 32;
+	float m = 0.f;
+	bool bad = false;
+	for (uint32_t k = 0; k < d; k++) {
+		const float v = x[(uint64_t)k * xstride];
+		if ((__builtin_bit_cast(uint32_t, v) & 0x7F800000u) == 0x7F800000u)
+			bad = true;
+		m = fmaxf(m, fabsf(v));
+	}
+	const bool covered =
+	    !bad && norm >= PF_NORM_MIN && norm <= PF_NORM_MAX && m > 0.f;
+	const float sc = covered ? (float)((double)m / 31.0)
+	                         : __builtin_bit_cast(float, 0x7FC00000u);
+	const double sd = (double)sc;
+	double res2 = 0.0;
+	uint32_t xs = 0;
+	for (uint32_t g = 0; g < G; g++) {
+		uint32_t hw[4] = {0, 0, 0, 0}, lw[2] = {0, 0};
+#pragma unroll
+		for (uint32_t i = 0; i < 32; i++) {
+			const uint32_t k = 32 * g + i;
+			uint32_t xu = 32;
+			if (covered && k < d) {
+				const double xv = (double)x[(uint64_t)k * xstride];
+				double c = rint(xv / sd);
+				c = c > 31.0 ? 31.0 : (c < -31.0 ? -31.0 : c);
+				const double r = xv - sd * c;
+				res2 += r * r;
+				xu = (uint32_t)((int)c + 32);
+			}
+			xs += xu;
+			hw[i >> 3] |= (xu >> 2) << (4 * (i & 7));
+			const uint32_t f = i & 15;
+			lw[i >> 4] |= (xu & 3u) << (2 * (f < 8 ? 2 * f : 2 * (f - 8) + 1));
+		}
+		for (int j = 0; j < 4; j++)
+			h[(uint64_t)g * hstride + j] = hw[j];
+		for (int j = 0; j < 2; j++)
+			l[(uint64_t)g * lstride + j] = lw[j];
+	}
+	*xsum = xs;
+	*scale = sc;
+	if (!covered) {
+		*pscale = sc;
+		*eps = 0.f;
+		return;
+	}
+	const double rho = sqrt(res2) / norm * (1.0 + 0x1p-40);
+	const double e =
+	    1.01 * (rho + 1.001 * (double)(d + 8) * 0x1p-24) + 0x1p-19;
+	*pscale = (float)(sd / norm);
+	*eps = pf_round_up_f32(e);
+}
+
+// Quantise a query for the int6 tier (host, once per call; q finite with a
+// norm q_norm inside the window, so maxabs > 0): sq = f32(maxabs / 2047),
+// cq_k = rint(q_k / sq) clamped to +-2047, qu_k = cq_k + 2048, padded
+// features qu = 2048. words (if not null) receives the digit dwords in the
+// order the planes need: words[g * 12 + t * 4 + m] holds digit t (0 = bits
+// 11..8, 1 = bits 7..4, 2 = bits 3..0) of features 32 g + 8 m + i in nibble
+// i. *rho = |q - sq cq| / q_norm in f64, rounded up to f32; *qs = sum qu_k
+// over the padded query.
+static void pf_q12(const float *q, uint32_t d, double q_norm, uint32_t *words,
+                   int16_t *codes, float *sq, float *rho, uint32_t *qs) {
+	const uint32_t G = (d + 31) / 32;
+	float m = 0.f;
+	for (uint32_t k = 0; k < d; k++)
+		m = fmaxf(m, fabsf(q[k]));
+	const float s = (float)((double)m / 2047.0);
+	const double sd = (double)s;
+	double res2 = 0.0;
+	uint32_t sum = 0;
+	for (uint32_t g = 0; g < G; g++) {
+		uint32_t w[PF6_QWORDS] = {0};
+		for (uint32_t i = 0; i < 32; i++) {
+			const uint32_t k = 32 * g + i;
+			uint32_t qu = 2048;
+			if (k < d) {
+				const double qv = (double)q[k];
+				double c = rint(qv / sd);
+				c = c > 2047.0 ? 2047.0 : (c < -2047.0 ? -2047.0 : c);
+				const double r = qv - sd * c;
+				res2 += r * r;
+				qu = (uint32_t)((int)c + 2048);
+				if (codes)
+					codes[k] = (int16_t)c;
+			}
+			sum += qu;
+			const uint32_t sh = 4 * (i & 7), mw = i >> 3;
+			w[0 + mw] |= (qu >> 8) << sh;
+			w[4 + mw] |= ((qu >> 4) & 15u) << sh;
+			w[8 + mw] |= (qu & 15u) << sh;
+		}
+		if (words)
+			std::memcpy(words + (uint64_t)g * PF6_QWORDS, w, sizeof(w));
+	}
+	*sq = s;
+	*qs = sum;
+	const double r = sqrt(res2) / q_norm * (1.0 + 0x1p-40);
+	*rho = r > 0.0 ? pf_round_up_f32(r) : 0.f;
+}
+
+// Build the int6 shadow: one lane per row, as k_shadow_i8.
+__global__ void k_shadow_i6(const float *__restrict__ cm,
+                            const double *__restrict__ norms,
+                            uint32_t *__restrict__ hp,
+                            uint32_t *__restrict__ lp,
+                            float *__restrict__ pscale,
+                            float *__restrict__ peps,
+                            uint32_t *__restrict__ xsum, uint64_t n,
+                            uint64_t n_pad, uint64_t sn_pad, uint32_t d) {
+	const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (r >= sn_pad)
+		return;
+	const uint32_t G = (d + 31) / 32;
+	float sc, ps = __uint_as_float(0x7FC00000u), pe = 0.f;
+	uint32_t xs = 32u * 32u * G;
+	if (r < n) {
+		pf_i6_row(cm + r, n_pad, d, norms[r], hp + r * 4, sn_pad * 4,
+		          lp + r * 2, sn_pad * 2, &sc, &ps, &pe, &xs);
+	} else { // padding row: never covered
+		for (uint32_t g = 0; g < G; g++) {
+			*(uint4 *)(hp + ((uint64_t)g * sn_pad + r) * 4) = make_uint4(
+			    0x88888888u, 0x88888888u, 0x88888888u, 0x88888888u);
+			*(uint2 *)(lp + ((uint64_t)g * sn_pad + r) * 2) = make_uint2(0, 0);
+		}
+	}
+	pscale[r] = ps;
+	peps[r] = pe;
+	xsum[r] = xs;
+}
+
+// k_prefilter over the int6 shadow: one row per lane and sweep, one 16-byte
+// H load and one 8-byte L load per group of 32 features (a wave reads 1 KiB
+// + 512 B contiguous), PF6_UNROLL groups in flight, loaded non-temporal (the
+// shadow is read once per query; worth 0.02-0.05 ms of 1.03 at 10M x 768,
+// profiles/prefilter_i6.md). Six exact u32
+// accumulators: H and L against the query's three digits (qd, uniform:
+// scalar loads, used as the dots' scalar operand). Per row
+// S = 4 (256 A_h2 + 16 A_h1 + A_h0) + 256 A_l2 + 16 A_l1 + A_l0 = sum xu qu
+// and N = sum c cq = S - 2048 xsum + qbias, qbias = 65536 d_pad - 32 sum qu
+// (mod 2^32; N fits int32). a = 1 - f32(N) * pscale * qscale, bounds
+// a +- e with e = peps + (1 + peps) qeps (proof above pf_i6_row). Upper
+// bounds go to the block top-K, lower bounds to scores[], exactly as in
+// k_prefilter_i8. A block collects the rows of PF6_SWEEPS sweeps that beat
+// its current Kth upper bound, then runs one select: the same 17 KB buffer.
+__global__ __launch_bounds__(THREADS) void k_prefilter_i6(
+    const uint4 *__restrict__ hp, const uint2 *__restrict__ lp,
+    const float *__restrict__ pscale, const float *__restrict__ peps,
+    const uint32_t *__restrict__ xsum, uint64_t n, uint64_t sn_pad,
+    uint32_t ngroups, const uint32_t *__restrict__ qd, float qscale,
+    float qeps, uint32_t qbias, uint32_t k, uint64_t rows_per_block,
+    float *__restrict__ scores, Cand *__restrict__ block_out,
+    uint32_t *__restrict__ cand_cnt) {
+	__shared__ uint64_t buf[PF_TILE + MAX_K];
+	__shared__ uint64_t topk[MAX_K];
+	__shared__ int cnt;
+	__shared__ int topk_n;
+	__shared__ uint64_t kth;
+
+	if (threadIdx.x == 0) {
+		cnt = 0;
+		topk_n = 0;
+		kth = ~0ULL;
+		if (blockIdx.x == 0)
+			*cand_cnt = 0;
+	}
+	__syncthreads();
+
+	uint64_t row_begin = (uint64_t)blockIdx.x * rows_per_block;
+	uint64_t row_end = row_begin + rows_per_block;
+	if (row_end > n)
+		row_end = n;
+	const float ninf = __uint_as_float(0xFF800000u);
+
+	for (uint64_t tile_base = row_begin; tile_base < row_end;
+	     tile_base += PF6_TILE) {
+		const uint64_t kthv = kth;
+		const int full = (topk_n >= (int)k);
+		for (int s = 0; s < PF6_SWEEPS; s++) {
+			const uint64_t sbase = tile_base + (uint64_t)s * THREADS;
+			if (sbase >= row_end)
+				break; // uniform
+			const uint64_t r = sbase + threadIdx.x; // < sn_pad
+			const uint4 *ph = hp + r;
+			const uint2 *pl = lp + r;
+			uint32_t ah2 = 0, ah1 = 0, ah0 = 0, al2 = 0, al1 = 0, al0 = 0;
+#define PF6_DOT3(X, m, a2, a1, a0)                                             \
+	a2 = __builtin_amdgcn_udot8((X), qw[0 + (m)], a2, false);                  \
+	a1 = __builtin_amdgcn_udot8((X), qw[4 + (m)], a1, false);                  \
+	a0 = __builtin_amdgcn_udot8((X), qw[8 + (m)], a0, false);
+#define PF6_GROUP(HV, LV, gi)                                                  \
+	{                                                                          \
+		const uint32_t *qw = qd + (uint64_t)(gi) * PF6_QWORDS;                 \
+		PF6_DOT3((HV).x, 0, ah2, ah1, ah0)                                     \
+		PF6_DOT3((HV).y, 1, ah2, ah1, ah0)                                     \
+		PF6_DOT3((HV).z, 2, ah2, ah1, ah0)                                     \
+		PF6_DOT3((HV).w, 3, ah2, ah1, ah0)                                     \
+		PF6_DOT3((LV).x & 0x33333333u, 0, al2, al1, al0)                       \
+		PF6_DOT3(((LV).x >> 2) & 0x33333333u, 1, al2, al1, al0)                \
+		PF6_DOT3((LV).y & 0x33333333u, 2, al2, al1, al0)                       \
+		PF6_DOT3(((LV).y >> 2) & 0x33333333u, 3, al2, al1, al0)                \
+	}
+			uint32_t g = 0;
+			for (; g + PF6_UNROLL <= ngroups; g += PF6_UNROLL) {
+				pf6_v4 hv[PF6_UNROLL];
+				pf6_v2 lv[PF6_UNROLL];
+#pragma unroll
+				for (uint32_t j = 0; j < PF6_UNROLL; j++) {
+					hv[j] = __builtin_nontemporal_load(
+					    (const pf6_v4 *)(ph + (uint64_t)(g + j) * sn_pad));
+					lv[j] = __builtin_nontemporal_load(
+					    (const pf6_v2 *)(pl + (uint64_t)(g + j) * sn_pad));
+				}
+#pragma unroll
+				for (uint32_t j = 0; j < PF6_UNROLL; j++)
+					PF6_GROUP(hv[j], lv[j], g + j)
+			}
+			for (; g < ngroups; g++) {
+				const uint4 hv1 = ph[(uint64_t)g * sn_pad];
+				const uint2 lv1 = pl[(uint64_t)g * sn_pad];
+				PF6_GROUP(hv1, lv1, g)
+			}
+#undef PF6_GROUP
+#undef PF6_DOT3
+			const uint32_t S = 4u * (256u * ah2 + 16u * ah1 + ah0) +
+			                   256u * al2 + 16u * al1 + al0;
+			const int32_t N = (int32_t)(S - 2048u * xsum[r] + qbias);
+			const float pe = peps[r];
+			const float a = __fsub_rn(
+			    1.0f, __fmul_rn(__fmul_rn((float)N, pscale[r]), qscale));
+			const float e =
+			    __fadd_rn(pe, __fmul_rn(__fadd_rn(1.0f, pe), qeps));
+			const bool ok = r < row_end &&
+			                (__float_as_uint(a) & 0x7F800000u) != 0x7F800000u;
+			scores[r] = ok ? __fsub_rn(a, e) : ninf;
+			if (ok) {
+				const uint64_t v =
+				    ((uint64_t)d_key32(__fadd_rn(a, e)) << 32) | (uint32_t)r;
+				if (!full || v < kthv) {
+					int idx = atomicAdd(&cnt, 1);
+					buf[idx] = v;
+				}
+			}
+		}
+		__syncthreads();
+
+		if (cnt > 0) {
+			int m = cnt;
+			for (int i = threadIdx.x; i < topk_n; i += THREADS)
+				buf[m + i] = topk[i];
+			int total = m + topk_n;
+			__syncthreads();
+			int new_n;
+			pf_block_select(buf, total, topk, (int)k, &new_n);
+			if (threadIdx.x == 0) {
+				topk_n = new_n;
+				if (new_n >= (int)k)
+					kth = topk[k - 1];
+				cnt = 0;
+			}
+		}
+		__syncthreads();
+	}
+
+	// block winners as Cand{upper bound, row} (pad with +inf) for k_merge
+	if (threadIdx.x < k) {
+		Cand c;
+		if ((int)threadIdx.x < topk_n) {
+			c.dist = (double)d_unkey32((uint32_t)(topk[threadIdx.x] >> 32));
+			c.id = (uint32_t)topk[threadIdx.x];
+		} else {
+			c.dist = __longlong_as_double(0x7FF0000000000000LL); // +inf
+			c.id = ~0ULL;
+		}
+		block_out[(uint64_t)blockIdx.x * k + threadIdx.x] = c;
+	}
+}
+
 // One pass over scores[]: append every row with score <= T_K + 2 eps to the
 // candidate list. bf16 tier: scores are a_i, approx_top[k-1].dist is A_K and
-// eps = pf_eps(d). int8 tier: scores are the lower bounds l_i,
+// eps = pf_eps(d). int8 and int6 tiers: scores are the lower bounds l_i,
 // approx_top[k-1].dist is U_K and eps = 0. T_K is +inf when fewer than K
 // rows carry a bound: then every row passes. The counter keeps counting past
 // PF_CAND_CAP; the list is never written past it.
@@ -2488,7 +2857,9 @@ static void free_table(Table &t) {
 	if (t.shadow8)
 		(void)hipFree(t.shadow8);
 	if (t.pscale)
-		(void)hipFree(t.pscale); // peps lives in the same allocation
+		(void)hipFree(t.pscale); // peps (and xsum) live in the same allocation
+	if (t.shadow6)
+		(void)hipFree(t.shadow6); // plane L lives in the same allocation
 	t = Table{};
 }
 
@@ -2612,9 +2983,14 @@ static void free_shadow(sdbv_ctx *ctx, Table *t) {
 		(void)hipFree(t->shadow8);
 	if (t->pscale)
 		(void)hipFree(t->pscale);
+	if (t->shadow6)
+		(void)hipFree(t->shadow6);
 	t->shadow = nullptr;
 	t->pinv = nullptr;
 	t->shadow8 = nullptr;
+	t->shadow6 = nullptr;
+	t->shadow6l = nullptr;
+	t->xsum = nullptr;
 	t->pscale = nullptr;
 	t->peps = nullptr;
 	t->bytes -= t->shadow_bytes;
@@ -2631,7 +3007,7 @@ static int build_shadow(sdbv_ctx *ctx, Table *t) {
 		return SDBV_ERR_UNSUPPORTED;
 	if (t->shadow)
 		return SDBV_OK;
-	if (t->shadow8)
+	if (t->shadow8 || t->shadow6)
 		free_shadow(ctx, t);
 	uint64_t sn_pad = ((t->n + PF_TILE - 1) / PF_TILE) * PF_TILE;
 	if (sn_pad == 0)
@@ -2666,7 +3042,7 @@ static int build_shadow_i8(sdbv_ctx *ctx, Table *t) {
 		return SDBV_ERR_UNSUPPORTED;
 	if (t->shadow8)
 		return SDBV_OK;
-	if (t->shadow)
+	if (t->shadow || t->shadow6)
 		free_shadow(ctx, t);
 	uint64_t sn_pad = ((t->n + PF8_TILE - 1) / PF8_TILE) * PF8_TILE;
 	if (sn_pad == 0)
@@ -2689,6 +3065,46 @@ static int build_shadow_i8(sdbv_ctx *ctx, Table *t) {
 	hipLaunchKernelGGL(k_shadow_i8, dim3((uint32_t)(sn_pad / 256)), dim3(256),
 	                   0, ctx->stream, t->cm, t->norms, t->shadow8, t->pscale,
 	                   t->peps, t->n, t->n_pad, sn_pad, t->d);
+	HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+	HIP_CHECK(ctx, hipGetLastError());
+	refresh_bytes_staged(ctx);
+	return SDBV_OK;
+}
+
+// The int6 shadow instead: 0.75 * d_pad + 12 bytes per row, d_pad = d rounded
+// up to a multiple of 32. Same contract.
+static int build_shadow_i6(sdbv_ctx *ctx, Table *t) {
+	if (t->metric != SDBV_METRIC_COSINE)
+		return SDBV_ERR_UNSUPPORTED;
+	if (t->shadow6)
+		return SDBV_OK;
+	if (t->shadow || t->shadow8)
+		free_shadow(ctx, t);
+	uint64_t sn_pad = ((t->n + PF6_TILE - 1) / PF6_TILE) * PF6_TILE;
+	if (sn_pad == 0)
+		sn_pad = PF6_TILE;
+	const uint64_t G = (t->d + 31) / 32;
+	uint64_t h_bytes = G * sn_pad * 16, l_bytes = G * sn_pad * 8;
+	uint64_t side_bytes = 3 * sn_pad * sizeof(float);
+	if (hipMalloc(&t->shadow6, h_bytes + l_bytes) != hipSuccess ||
+	    hipMalloc(&t->pscale, side_bytes) != hipSuccess) {
+		(void)hipGetLastError(); // allocation failure is not sticky
+		if (t->shadow6)
+			(void)hipFree(t->shadow6);
+		t->shadow6 = nullptr;
+		t->pscale = nullptr;
+		return SDBV_ERR_OOM;
+	}
+	t->shadow6l = t->shadow6 + h_bytes / sizeof(uint32_t);
+	t->peps = t->pscale + sn_pad;
+	t->xsum = (uint32_t *)(t->peps + sn_pad);
+	t->sn_pad = sn_pad;
+	t->shadow_bytes = h_bytes + l_bytes + side_bytes;
+	t->bytes += t->shadow_bytes;
+	hipLaunchKernelGGL(k_shadow_i6, dim3((uint32_t)(sn_pad / 256)), dim3(256),
+	                   0, ctx->stream, t->cm, t->norms, t->shadow6,
+	                   t->shadow6l, t->pscale, t->peps, t->xsum, t->n,
+	                   t->n_pad, sn_pad, t->d);
 	HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
 	HIP_CHECK(ctx, hipGetLastError());
 	refresh_bytes_staged(ctx);
@@ -2735,6 +3151,24 @@ static bool shadow_policy_i8(const Table *t) {
 	return t->n >= min_rows;
 }
 
+// Default minimum row count from which the shadow that staging builds is the
+// int6 one, given that the int8 policy holds: the measured crossover against
+// the int8 tier (profiles/prefilter_i6.md); never below PF_DEFAULT_MIN_ROWS.
+#define PF6_DEFAULT_MIN_ROWS 500000ull
+
+// SDBV_SCAN_PREFILTER_I6=0 keeps int8; SDBV_SCAN_PREFILTER_I6_MIN_ROWS
+// overrides the int6 minimum row count (independent of the other two).
+static bool shadow_policy_i6(const Table *t) {
+	const char *e = getenv("SDBV_SCAN_PREFILTER_I6");
+	if (e && e[0] == '0' && e[1] == 0)
+		return false;
+	uint64_t min_rows = PF6_DEFAULT_MIN_ROWS;
+	const char *m = getenv("SDBV_SCAN_PREFILTER_I6_MIN_ROWS");
+	if (m && *m)
+		min_rows = strtoull(m, nullptr, 10);
+	return t->n >= min_rows;
+}
+
 static int finish_stage(sdbv_ctx *ctx, Table *t, bool scan_table) {
 	uint64_t nb = (t->n + THREADS - 1) / THREADS;
 	if (t->metric == SDBV_METRIC_COSINE) {
@@ -2756,8 +3190,9 @@ static int finish_stage(sdbv_ctx *ctx, Table *t, bool scan_table) {
 	// a table staged for scanning gets the prefilter shadow when the policy
 	// asks for one; without the memory for it the table simply has none
 	if (scan_table && shadow_policy(t)) {
-		int rc = shadow_policy_i8(t) ? build_shadow_i8(ctx, t)
-		                             : build_shadow(ctx, t);
+		int rc = !shadow_policy_i8(t)  ? build_shadow(ctx, t)
+		         : shadow_policy_i6(t) ? build_shadow_i6(ctx, t)
+		                               : build_shadow_i8(ctx, t);
 		if (rc != SDBV_OK && rc != SDBV_ERR_OOM)
 			return rc;
 	}
@@ -2817,7 +3252,7 @@ int sdbv_table_set_prefilter(sdbv_ctx *ctx, uint64_t table, int on) {
 		return SDBV_ERR_UNSUPPORTED;
 	if (on)
 		return build_shadow(ctx, t);
-	if (t->shadow || t->shadow8)
+	if (t->shadow || t->shadow8 || t->shadow6)
 		free_shadow(ctx, t);
 	return SDBV_OK;
 }
@@ -2834,6 +3269,16 @@ int sdbv_table_set_prefilter_kind(sdbv_ctx *ctx, uint64_t table, int kind) {
 	return build_shadow_i8(ctx, &it->second);
 }
 
+// The int6 shadow has an entry of its own: sdbv_table_set_prefilter_kind
+// keeps rejecting every kind above 2, as its callers rely on.
+int sdbv_table_set_prefilter_i6(sdbv_ctx *ctx, uint64_t table) {
+	std::lock_guard<std::mutex> lk(ctx->mu);
+	auto it = ctx->tables.find(table);
+	if (it == ctx->tables.end())
+		return SDBV_ERR_NO_TABLE;
+	return build_shadow_i6(ctx, &it->second);
+}
+
 float sdbv_prefilter_eps(uint32_t d) { return pf_eps(d); }
 
 int sdbv_prefilter_i8_row(const float *x, uint32_t d, double norm,
@@ -2845,6 +3290,43 @@ int sdbv_prefilter_i8_row(const float *x, uint32_t d, double norm,
 	pf_i8_row(x, 1, d, norm, stored, 1, scale, &pscale, eps);
 	for (uint32_t k = 0; k < d; k++)
 		codes[k] = (int8_t)((int)stored[k] - 128);
+	return SDBV_OK;
+}
+
+int sdbv_prefilter_i6_row(const float *x, uint32_t d, double norm,
+                          int8_t *codes, float *scale, float *eps,
+                          uint32_t *xsum) {
+	if (!x || !codes || !scale || !eps || !xsum || d == 0 || d > MAX_D)
+		return SDBV_ERR_BAD_ARG;
+	uint32_t h[MAX_D / 32 * 4], l[MAX_D / 32 * 2];
+	float pscale;
+	pf_i6_row(x, 1, d, norm, h, 4, l, 2, scale, &pscale, eps, xsum);
+	for (uint32_t k = 0; k < d; k++) {
+		const uint32_t g = k / 32, i = k % 32, f = i & 15;
+		const uint32_t hi = (h[g * 4 + (i >> 3)] >> (4 * (i & 7))) & 15u;
+		const uint32_t lo =
+		    (l[g * 2 + (i >> 4)] >> (2 * (f < 8 ? 2 * f : 2 * (f - 8) + 1))) &
+		    3u;
+		codes[k] = (int8_t)((int)(hi * 4 + lo) - 32);
+	}
+	return SDBV_OK;
+}
+
+int sdbv_prefilter_q12(const float *q, uint32_t d, int16_t *codes, float *sq,
+                       float *rho_q, uint32_t *qs) {
+	if (!q || !codes || !sq || !rho_q || !qs || d == 0 || d > MAX_D)
+		return SDBV_ERR_BAD_ARG;
+	const double q_norm = sqrt((double)h_sumsq_f32(q, d));
+	if (!(q_norm >= PF_NORM_MIN && q_norm <= PF_NORM_MAX)) {
+		// the prefilter never runs for such a query
+		for (uint32_t k = 0; k < d; k++)
+			codes[k] = 0;
+		*sq = __builtin_bit_cast(float, 0x7FC00000u);
+		*rho_q = 0.f;
+		*qs = 2048u * 32u * ((d + 31) / 32);
+		return SDBV_OK;
+	}
+	pf_q12(q, d, q_norm, nullptr, codes, sq, rho_q, qs);
 	return SDBV_OK;
 }
 
@@ -2905,10 +3387,13 @@ static int ensure_query_scratch(sdbv_ctx *ctx, uint32_t d, uint64_t nblocks,
 	if (ctx->q_cap < d) {
 		if (ctx->q_dev)
 			(void)hipFree(ctx->q_dev);
-		HIP_CHECK(ctx, hipMalloc(&ctx->q_dev, d * sizeof(float)));
+		// the query, then the int6 tier's digit words (one H2D copy)
+		const size_t qb = d * sizeof(float) +
+		                  (size_t)((d + 31) / 32) * PF6_QWORDS * sizeof(uint32_t);
+		HIP_CHECK(ctx, hipMalloc(&ctx->q_dev, qb));
 		if (ctx->q_pin)
 			(void)hipHostFree(ctx->q_pin);
-		HIP_CHECK(ctx, hipHostMalloc(&ctx->q_pin, d * sizeof(float)));
+		HIP_CHECK(ctx, hipHostMalloc(&ctx->q_pin, qb));
 		ctx->q_cap = d;
 	}
 	uint64_t need = nblocks * k * sizeof(Cand);
@@ -3026,15 +3511,20 @@ static int knn_large_k(sdbv_ctx *ctx, Table &t, const float *q, uint32_t d,
 // block the same span). A grid of a few more blocks than the chip holds runs
 // a second, mostly empty round with too few bytes in flight per CU — 3.5 %
 // of the kernel at 10M rows (profiles/prefilter_scan.md).
-static uint64_t prefilter_grid(sdbv_ctx *ctx, uint64_t n, bool i8,
+static uint64_t prefilter_grid(sdbv_ctx *ctx, uint64_t n, int kind,
                                uint64_t *rows_per_block) {
-	uint64_t &slots = i8 ? ctx->pf8_slots : ctx->pf_slots;
+	uint64_t &slots = kind == 3   ? ctx->pf6_slots
+	                  : kind == 2 ? ctx->pf8_slots
+	                              : ctx->pf_slots;
 	if (slots == 0) {
 		int per_cu = 0, cus = 0;
-		hipError_t e = i8 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(
-		                        &per_cu, k_prefilter_i8, THREADS, 0)
-		                  : hipOccupancyMaxActiveBlocksPerMultiprocessor(
-		                        &per_cu, k_prefilter, THREADS, 0);
+		hipError_t e =
+		    kind == 3   ? hipOccupancyMaxActiveBlocksPerMultiprocessor(
+		                      &per_cu, k_prefilter_i6, THREADS, 0)
+		    : kind == 2 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(
+		                      &per_cu, k_prefilter_i8, THREADS, 0)
+		                : hipOccupancyMaxActiveBlocksPerMultiprocessor(
+		                      &per_cu, k_prefilter, THREADS, 0);
 		if (e != hipSuccess ||
 		    hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount,
 		                          ctx->device) != hipSuccess ||
@@ -3045,7 +3535,7 @@ static uint64_t prefilter_grid(sdbv_ctx *ctx, uint64_t n, bool i8,
 			slots = (uint64_t)per_cu * (uint64_t)cus;
 		}
 	}
-	const uint64_t tile = i8 ? PF8_TILE : PF_TILE;
+	const uint64_t tile = kind == 3 ? PF6_TILE : kind == 2 ? PF8_TILE : PF_TILE;
 	uint64_t tiles = (n + tile - 1) / tile;
 	uint64_t nblocks = tiles < slots ? tiles : slots;
 	if (nblocks == 0)
@@ -3061,9 +3551,21 @@ static uint64_t prefilter_grid(sdbv_ctx *ctx, uint64_t n, bool i8,
 // exact top-k, *ncand the candidate count; *ncand > PF_CAND_CAP means the
 // list overflowed and host_out is void: the caller runs the exact scan.
 // One D2H copy and one sync, like the exact path. Caller holds ctx->mu.
+struct PfQ6 { // int6 tier: the quantised query's kernel operands
+	float qscale = 0.f; // f32(sq / |q|)
+	float qeps = 0.f;   // 1.01 rho_q, rounded up
+	uint32_t bias = 0;  // 65536 d_pad - 32 sum qu (mod 2^32)
+};
+
+static inline int shadow_kind(const Table &t) {
+	return t.shadow6 ? 3 : t.shadow8 ? 2 : t.shadow ? 1 : 0;
+}
+
 static int knn_prefilter(sdbv_ctx *ctx, Table &t, uint32_t k, double q_norm,
-                         float qbias, Cand *host_out, uint32_t *ncand) {
-	const bool i8 = t.shadow8 != nullptr;
+                         float qbias, const PfQ6 &q6, Cand *host_out,
+                         uint32_t *ncand) {
+	const int kind = shadow_kind(t);
+	const bool i8 = kind >= 2; // per-row bounds: zero compact window
 	if (ctx->pf_scores_cap < t.sn_pad) {
 		if (ctx->pf_scores)
 			(void)hipFree(ctx->pf_scores);
@@ -3081,7 +3583,7 @@ static int knn_prefilter(sdbv_ctx *ctx, Table &t, uint32_t k, double q_norm,
 		HIP_CHECK(ctx, hipMalloc(&ctx->pf_res, (MAX_K + 2) * sizeof(Cand)));
 
 	uint64_t rows_per_block = 0;
-	uint64_t nblocks = prefilter_grid(ctx, t.n, i8, &rows_per_block);
+	uint64_t nblocks = prefilter_grid(ctx, t.n, kind, &rows_per_block);
 	Cand *res = (Cand *)ctx->pf_res;
 	// device counter: behind the k results and the copy of the count that
 	// k_pf_final appends to them
@@ -3089,7 +3591,15 @@ static int knn_prefilter(sdbv_ctx *ctx, Table &t, uint32_t k, double q_norm,
 	const float inv_q = (float)(1.0 / q_norm);
 
 	HIP_CHECK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-	if (i8)
+	if (kind == 3)
+		hipLaunchKernelGGL(k_prefilter_i6, dim3((uint32_t)nblocks),
+		                   dim3(THREADS), 0, ctx->stream,
+		                   (const uint4 *)t.shadow6, (const uint2 *)t.shadow6l,
+		                   t.pscale, t.peps, t.xsum, t.n, t.sn_pad,
+		                   (t.d + 31) / 32, (const uint32_t *)(ctx->q_dev + t.d),
+		                   q6.qscale, q6.qeps, q6.bias, k, rows_per_block,
+		                   ctx->pf_scores, (Cand *)ctx->block_out, cand_cnt);
+	else if (kind == 2)
 		hipLaunchKernelGGL(k_prefilter_i8, dim3((uint32_t)nblocks),
 		                   dim3(THREADS), 0, ctx->stream, t.shadow8, t.pscale,
 		                   t.peps, t.n, t.sn_pad, t.d, ctx->q_dev, inv_q, qbias,
@@ -3239,38 +3749,54 @@ int sdbv_knn_bruteforce(sdbv_ctx *ctx, uint64_t table, const float *q,
 	uint64_t pf_rows_per_block = 0;
 	uint64_t scratch_blocks = std::max(
 	    nblocks,
-	    prefilter_grid(ctx, t.n, t.shadow8 != nullptr, &pf_rows_per_block));
+	    prefilter_grid(ctx, t.n, shadow_kind(t), &pf_rows_per_block));
 	int rc = ensure_query_scratch(ctx, d, scratch_blocks, k);
 	if (rc != SDBV_OK)
 		return rc;
-	std::memcpy(ctx->q_pin, q, d * sizeof(float)); // pinned staging
-	HIP_CHECK(ctx, hipMemcpyAsync(ctx->q_dev, ctx->q_pin, d * sizeof(float),
-	                              hipMemcpyHostToDevice, ctx->stream));
 	double q_norm = sqrt((double)h_sumsq_f32(q, d));
-
-	auto t_start = std::chrono::steady_clock::now();
-	Cand host_out[MAX_K + 1];
 	// Prefilter path: a shadowed cosine table and a query whose norm lies in
 	// the window the bound is proven for (a non-finite element makes the
 	// norm non-finite). Everything else, and a query whose candidate list
 	// overflowed, takes the exact scan; results never depend on the choice.
-	if ((t.shadow || t.shadow8) && q_norm >= PF_NORM_MIN &&
-	    q_norm <= PF_NORM_MAX) {
+	const int kind = shadow_kind(t);
+	const bool use_pf =
+	    kind != 0 && q_norm >= PF_NORM_MIN && q_norm <= PF_NORM_MAX;
+	std::memcpy(ctx->q_pin, q, d * sizeof(float)); // pinned staging
+	size_t q_bytes = d * sizeof(float);
+	PfQ6 q6;
+	if (use_pf && kind == 3) {
+		// int6 tier: the query's digit words ride behind it in the same copy
+		const uint32_t G = (d + 31) / 32;
+		float sq, rho;
+		uint32_t qs;
+		pf_q12(q, d, q_norm, (uint32_t *)(ctx->q_pin + d), nullptr, &sq, &rho,
+		       &qs);
+		q_bytes += (size_t)G * PF6_QWORDS * sizeof(uint32_t);
+		q6.qscale = (float)((double)sq / q_norm);
+		q6.qeps = rho > 0.f ? pf_round_up_f32(1.01 * (double)rho) : 0.f;
+		q6.bias = 65536u * (32u * G) - 32u * qs;
+	}
+	HIP_CHECK(ctx, hipMemcpyAsync(ctx->q_dev, ctx->q_pin, q_bytes,
+	                              hipMemcpyHostToDevice, ctx->stream));
+
+	auto t_start = std::chrono::steady_clock::now();
+	Cand host_out[MAX_K + 1];
+	if (use_pf) {
 		// int8 tier: the bias term 128 * sum q_k, one f64 sum rounded once
 		double qsum = 0.0;
 		if (t.shadow8)
 			for (uint32_t i = 0; i < d; i++)
 				qsum += (double)q[i];
 		uint32_t ncand = 0;
-		rc = knn_prefilter(ctx, t, k, q_norm, (float)(128.0 * qsum), host_out,
-		                   &ncand);
+		rc = knn_prefilter(ctx, t, k, q_norm, (float)(128.0 * qsum), q6,
+		                   host_out, &ncand);
 		if (rc != SDBV_OK)
 			return rc;
 		ctx->stats.last_prefilter_candidates = ncand;
 		ctx->stats.last_scan_path = (ncand <= PF_CAND_CAP ? 1u : 2u) +
-		                            (t.shadow8 ? 2u : 0u);
+		                            2u * (uint32_t)(kind - 1);
 	}
-	if (ctx->stats.last_scan_path != 1 && ctx->stats.last_scan_path != 3) {
+	if (!(ctx->stats.last_scan_path & 1u)) {
 		rc = knn_exact_scan(ctx, t, k, q_norm, nblocks, rows_per_block,
 		                    host_out);
 		if (rc != SDBV_OK)
