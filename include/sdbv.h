@@ -10,6 +10,8 @@
  *    legacy KnnPriorityList path surrealdb/core/src/idx/planner/knn.rs:11-106).
  *    The host keeps: record streaming, Value->vector extraction
  *    (knn_topk.rs:274-288), WHERE filtering, and record materialisation.
+ *    sdbv_knn_bruteforce_filtered takes the outcome of that filtering (and
+ *    the rows deleted since staging) as an allowed-row bitmap.
  *  - sdbv_stage_corpus replaces the per-search scattered vector access of
  *    the reference (VectorCache LRU + He KV keys,
  *    surrealdb/core/src/idx/trees/hnsw/cache.rs,
@@ -93,7 +95,12 @@ typedef struct sdbv_stats {
 	                            exact scan, 3 = int8 prefilter, 4 = int8
 	                            prefilter overflowed, then exact scan, 5 = int6
 	                            prefilter, 6 = int6 prefilter overflowed, then
-	                            exact scan */
+	                            exact scan. sdbv_knn_bruteforce_filtered: 7 =
+	                            masked scan, 8 = row-list path, 0 = the
+	                            all-distances route */
+	uint64_t last_filter_rows; /* allowed rows of the last filtered call (for
+	                              such a call last_rows_scanned is the same
+	                              count) */
 } sdbv_stats;
 
 /* Create a context on HIP device `device` (-1 = current device). */
@@ -231,6 +238,41 @@ void sdbv_gen_f32(uint64_t seed, uint64_t row0, uint64_t nrows, uint32_t d,
 int sdbv_knn_bruteforce(sdbv_ctx *, uint64_t table, const float *q, uint32_t d,
                         uint32_t k, uint64_t *out_ids, double *out_dists,
                         uint32_t *out_n);
+
+/* Filtered brute-force: sdbv_knn_bruteforce restricted to the rows a bitmap
+ * allows. The reference's KnnTopK (knn_topk.rs:166-267) ranks the stream the
+ * planner hands it, i.e. the rows that survive the residual WHERE and are not
+ * deleted; this call gives a table staged once the same meaning.
+ * `allow` is a bitmap over ROW POSITIONS of the staged table: row r is
+ * allowed iff bit (r & 63) of word (r >> 6) is set. Staged ids are strictly
+ * increasing, so the host's id -> row map is the rank of the id (row == id
+ * when the table was staged with ids == NULL). allow_words must equal
+ * ceil(n / 64); anything else, or allow == NULL, is SDBV_ERR_BAD_ARG. Bits at
+ * positions >= n in the last word are ignored.
+ * Result contract: that of sdbv_knn_bruteforce over the allowed rows only —
+ * ascending (distance f64 total_cmp, id), distance bits of the exact chain,
+ * *out_n = min(k, allowed rows); no allowed row gives *out_n = 0, SDBV_OK and
+ * no launch. The exact f32 store serves every filtered call; a prefilter
+ * shadow is neither used nor disturbed.
+ * COSINE/EUCLIDEAN with k <= 64 run on-device: at most
+ * SDBV_FILTER_ROWLIST_MAX allowed rows (environment, read at each call,
+ * default and ceiling 16384; 0 = never) are listed by the host and gathered
+ * one workgroup per row (last_scan_path 8); more run the masked scan, k_scan
+ * with the bitmap as a second validity test, which skips every 256-row
+ * segment without an allowed row (last_scan_path 7). Other metrics and larger
+ * k take the all-distances launch with a host selection that skips the rows
+ * not allowed (last_scan_path 0). */
+int sdbv_knn_bruteforce_filtered(sdbv_ctx *, uint64_t table, const float *q,
+                                 uint32_t d, uint32_t k,
+                                 const uint64_t *allow, uint64_t allow_words,
+                                 uint64_t *out_ids, double *out_dists,
+                                 uint32_t *out_n);
+/* Host-only: the bitmap walk of the filtered call. Returns the number of
+ * allowed rows below n and writes the first min(count, cap) of them to
+ * out_rows in ascending order (out_rows may be NULL with cap 0). Bits at or
+ * past n are ignored. */
+uint64_t sdbv_filter_rows(const uint64_t *allow, uint64_t allow_words,
+                          uint64_t n, uint32_t *out_rows, uint64_t cap);
 
 /* Batched-query brute-force: Q is b x d row-major; out_ids/out_dists are
  * b x k row-major. The dense Q x corpus^T product runs on MFMA. */

@@ -54,6 +54,7 @@ class _Stats(ctypes.Structure):
         ("last_rows_scanned", ctypes.c_uint64),
         ("last_prefilter_candidates", ctypes.c_uint64),
         ("last_scan_path", ctypes.c_uint32),
+        ("last_filter_rows", ctypes.c_uint64),
     ]
 
 
@@ -104,6 +105,10 @@ def lib():
     L.sdbv_bf16_rne.restype = ctypes.c_float
     L.sdbv_bf16_rne.argtypes = [ctypes.c_float]
     L.sdbv_knn_bruteforce.argtypes = [vp, u64, f32p, u32, u32, u64p, f64p, u32p]
+    L.sdbv_knn_bruteforce_filtered.argtypes = [vp, u64, f32p, u32, u32, u64p,
+                                               u64, u64p, f64p, u32p]
+    L.sdbv_filter_rows.restype = u64
+    L.sdbv_filter_rows.argtypes = [u64p, u64, u64, u32p, u64]
     L.sdbv_all_distances.argtypes = [vp, u64, f32p, u32, f64p]
     L.sdbv_gather_distance.argtypes = [vp, u64, u32p, u32, f32p, u32, f64p]
     L.sdbv_knn_batch.argtypes = [vp, u64, f32p, u32, u32, u32, u64p, f64p]
@@ -286,6 +291,27 @@ class Context:
         m = out_n.value
         return ids[:m], dists[:m]
 
+    def knn_bruteforce_filtered(self, table, q, k, allow):
+        """knn_bruteforce over the allowed rows only. `allow` is a bool
+        array with one entry per staged row, or the ready uint64 bitmap
+        (row r = bit r & 63 of word r >> 6). Returns (ids, dists)."""
+        import numpy as np
+        q = np.ascontiguousarray(q, dtype=np.float32)
+        n = self.table_rows(table)
+        words = _allow_words(allow, n)
+        ids = np.empty(k, dtype=np.uint64)
+        dists = np.empty(k, dtype=np.float64)
+        out_n = ctypes.c_uint32(0)
+        _check(self._ptr, lib().sdbv_knn_bruteforce_filtered(
+            self._ptr, table, q.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
+            q.size, k,
+            words.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), words.size,
+            ids.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)),
+            dists.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+            ctypes.byref(out_n)), "sdbv_knn_bruteforce_filtered")
+        m = out_n.value
+        return ids[:m], dists[:m]
+
     def all_distances(self, table, q):
         import numpy as np
         q = np.ascontiguousarray(q, dtype=np.float32)
@@ -336,6 +362,45 @@ class Context:
             dists.ctypes.data_as(ctypes.POINTER(ctypes.c_double))),
             "sdbv_knn_batch")
         return ids, dists
+
+
+def _allow_words(allow, n):
+    """The allowed-row bitmap of an n-row table as ceil(n / 64) uint64 words:
+    a bool array of length n is packed little-endian (row r = bit r & 63 of
+    word r >> 6); a uint64 array is taken as the ready bitmap."""
+    import numpy as np
+    a = np.asarray(allow)
+    nwords = (int(n) + 63) // 64
+    if a.dtype == np.uint64:
+        if a.ndim != 1 or a.size != nwords:
+            raise SdbvError(
+                f"allow: {a.size} bitmap words for {n} rows, need {nwords}")
+        return np.ascontiguousarray(a)
+    if a.dtype != np.bool_:
+        raise SdbvError(f"allow: bool or uint64 array expected, got {a.dtype}")
+    if a.ndim != 1 or a.size != n:
+        raise SdbvError(f"allow: {a.size} entries for {n} rows")
+    packed = np.zeros(nwords * 8, dtype=np.uint8)
+    bits = np.packbits(a, bitorder="little")
+    packed[:bits.size] = bits
+    return packed.view("<u8").astype(np.uint64, copy=False)
+
+
+def filter_rows(allow, n, cap=None):
+    """Host-only bitmap walk of the filtered scan: (count, rows). count is
+    the number of allowed rows below n (bits at or past n are ignored); rows
+    holds the first min(count, cap) of them ascending (cap None = all)."""
+    import numpy as np
+    words = _allow_words(allow, n)
+    u64p = ctypes.POINTER(ctypes.c_uint64)
+    if cap is None:
+        cap = lib().sdbv_filter_rows(words.ctypes.data_as(u64p), words.size,
+                                     n, None, 0)
+    rows = np.empty(max(int(cap), 1), dtype=np.uint32)
+    count = lib().sdbv_filter_rows(
+        words.ctypes.data_as(u64p), words.size, n,
+        rows.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), int(cap))
+    return int(count), rows[:min(int(count), int(cap))]
 
 
 def prefilter_eps(d):

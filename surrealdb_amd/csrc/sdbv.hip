@@ -159,6 +159,14 @@ struct sdbv_ctx {
 	uint32_t *bcand_cnt = nullptr; // [b]
 	uint64_t bcand_cnt_cap = 0;
 	double ms_gemm = 0, ms_select = 0, ms_exact = 0; // last batch timings
+	// filtered brute-force scratch (sdbv_knn_bruteforce_filtered), its own:
+	// nothing here is shared with the prefilter tiers
+	uint64_t *flt_mask = nullptr;     // [n_pad / 64] allowed-row bitmap, device
+	uint64_t *flt_mask_pin = nullptr; // pinned copy with the tail bits cleared
+	uint64_t flt_mask_cap = 0;        // words, both buffers
+	uint32_t *flt_rows = nullptr;     // [PF_CAND_CAP] allowed rows, device
+	uint32_t *flt_rows_pin = nullptr; // pinned: the host builds the list here
+	void *flt_cands = nullptr;        // [PF_CAND_CAP] Cand of the listed rows
 };
 
 struct Cand {
@@ -1595,6 +1603,252 @@ __global__ __launch_bounds__(THREADS) void k_pf_final(
 	merge_slice(cands, total, k, total, out);
 }
 
+// ---------------------------------------------------------------------------
+// Filtered brute-force scan (sdbv_knn_bruteforce_filtered):
+// exact top-K over the rows an allowed-row bitmap names. Exact f32 store
+// only, never a shadow.
+// ---------------------------------------------------------------------------
+
+// Masked scan: k_scan with one more reason for a row to be invalid. Same
+// span-per-block grid, LDS query, per-row chains, LCand buffer, select and
+// block_out format, so k_merge finishes it. mask holds n_pad / 64 words with
+// no bit set at or past n (the host clears the tail and zero-fills behind
+// it). A lane's ROWS_PER_LANE rows start at a multiple of 4, so their bits
+// are one nibble of one word; a wave covers 256 consecutive rows = four
+// words, and when none of its lanes has a live row the wave skips the
+// feature loop: no corpus loads, no arithmetic. The branch is wave-uniform
+// (a ballot) and encloses only the feature loop, never a __syncthreads().
+template <int METRIC>
+__global__ __launch_bounds__(THREADS) void k_scan_masked(
+    const float *__restrict__ cm, const double *__restrict__ norms,
+    uint64_t n, uint64_t n_pad, uint32_t d, const float *__restrict__ qg,
+    double q_norm, uint32_t k, uint64_t rows_per_block,
+    Cand *__restrict__ block_out, const uint64_t *__restrict__ ids,
+    const uint64_t *__restrict__ mask) {
+	__shared__ float qs[MAX_D];
+	__shared__ LCand buf[TILE + MAX_K];
+	__shared__ LCand topk[MAX_K];
+	__shared__ int cnt;
+	__shared__ int topk_n;
+	__shared__ uint64_t kth_key;
+	__shared__ uint32_t kth_row;
+
+	for (uint32_t i = threadIdx.x; i < d; i += THREADS)
+		qs[i] = qg[i];
+	if (threadIdx.x == 0) {
+		cnt = 0;
+		topk_n = 0;
+		kth_key = ~0ULL;
+		kth_row = ~0u;
+	}
+	__syncthreads();
+
+	uint64_t row_begin = (uint64_t)blockIdx.x * rows_per_block;
+	uint64_t row_end = row_begin + rows_per_block;
+	if (row_end > n)
+		row_end = n;
+
+	for (uint64_t tile_base = row_begin; tile_base < row_end; tile_base += TILE) {
+		uint64_t r0 = tile_base + (uint64_t)threadIdx.x * ROWS_PER_LANE;
+		// r0 < n_pad: tile_base is a multiple of TILE below n <= n_pad
+		const uint32_t nib = (uint32_t)(mask[r0 >> 6] >> (r0 & 63)) & 0xFu;
+		double dist[ROWS_PER_LANE];
+		bool valid[ROWS_PER_LANE];
+		bool any = false;
+#pragma unroll
+		for (int c = 0; c < ROWS_PER_LANE; c++) {
+			valid[c] = (r0 + c) < row_end && ((nib >> c) & 1u);
+			any = any || valid[c];
+			dist[c] = 0.0;
+		}
+
+		if (__ballot(any) != 0ULL) {
+			if (METRIC == 0) {
+				// cosine: ndarray unrolled_dot restatement, as k_scan<0>
+				float4 p[8];
+#pragma unroll
+				for (int j = 0; j < 8; j++)
+					p[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+				uint32_t k8 = 0;
+				for (; k8 + 8 <= d; k8 += 8) {
+#pragma unroll
+					for (uint32_t j = 0; j < 8; j++) {
+						const float4 v = *(const float4 *)(cm +
+						    (uint64_t)(k8 + j) * n_pad + r0);
+						const float qk = qs[k8 + j];
+						p[j].x = __fadd_rn(p[j].x, __fmul_rn(v.x, qk));
+						p[j].y = __fadd_rn(p[j].y, __fmul_rn(v.y, qk));
+						p[j].z = __fadd_rn(p[j].z, __fmul_rn(v.z, qk));
+						p[j].w = __fadd_rn(p[j].w, __fmul_rn(v.w, qk));
+					}
+				}
+				float4 sum = make_float4(0.f, 0.f, 0.f, 0.f);
+#define COMB(f)                                                                 \
+	sum.f = __fadd_rn(sum.f, __fadd_rn(p[0].f, p[4].f));                        \
+	sum.f = __fadd_rn(sum.f, __fadd_rn(p[1].f, p[5].f));                        \
+	sum.f = __fadd_rn(sum.f, __fadd_rn(p[2].f, p[6].f));                        \
+	sum.f = __fadd_rn(sum.f, __fadd_rn(p[3].f, p[7].f));
+				COMB(x) COMB(y) COMB(z) COMB(w)
+#undef COMB
+				for (; k8 < d; k8++) {
+					const float4 v =
+					    *(const float4 *)(cm + (uint64_t)k8 * n_pad + r0);
+					const float qk = qs[k8];
+					sum.x = __fadd_rn(sum.x, __fmul_rn(v.x, qk));
+					sum.y = __fadd_rn(sum.y, __fmul_rn(v.y, qk));
+					sum.z = __fadd_rn(sum.z, __fmul_rn(v.z, qk));
+					sum.w = __fadd_rn(sum.w, __fmul_rn(v.w, qk));
+				}
+				const float s[4] = {sum.x, sum.y, sum.z, sum.w};
+#pragma unroll
+				for (int c = 0; c < ROWS_PER_LANE; c++) {
+					double den = q_norm * norms[r0 + c < n_pad ? r0 + c : 0];
+					dist[c] = 1.0 - (double)s[c] / den;
+				}
+			} else {
+				// euclidean: the sequential f32 chain, as k_scan<1>
+				float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+				for (uint32_t kk = 0; kk < d; kk++) {
+					const float4 v =
+					    *(const float4 *)(cm + (uint64_t)kk * n_pad + r0);
+					const float qk = qs[kk];
+					float dx = v.x - qk, dy = v.y - qk, dz = v.z - qk,
+					      dw = v.w - qk;
+					acc.x = __fadd_rn(acc.x, __fmul_rn(dx, dx));
+					acc.y = __fadd_rn(acc.y, __fmul_rn(dy, dy));
+					acc.z = __fadd_rn(acc.z, __fmul_rn(dz, dz));
+					acc.w = __fadd_rn(acc.w, __fmul_rn(dw, dw));
+				}
+				const float s[4] = {acc.x, acc.y, acc.z, acc.w};
+#pragma unroll
+				for (int c = 0; c < ROWS_PER_LANE; c++)
+					dist[c] = sqrt((double)s[c]);
+			}
+		}
+
+		// threshold check + candidate append (rare path)
+		uint64_t kk_key = kth_key;
+		uint32_t kk_row = kth_row;
+		int full = (topk_n >= (int)k);
+#pragma unroll
+		for (int c = 0; c < ROWS_PER_LANE; c++) {
+			if (!valid[c])
+				continue;
+			uint64_t key = d_total_key(dist[c]);
+			uint32_t row32 = (uint32_t)(r0 + c);
+			bool take = !full || key < kk_key || (key == kk_key && row32 < kk_row);
+			if (take) {
+				int idx = atomicAdd(&cnt, 1);
+				buf[idx].key = key;
+				buf[idx].dist = dist[c];
+				buf[idx].row = row32;
+			}
+		}
+		__syncthreads();
+
+		// merge: all threads select new top-k from {candidates, current topk}
+		if (cnt > 0) {
+			int m = cnt;
+			for (int i = threadIdx.x; i < topk_n; i += THREADS)
+				buf[m + i] = topk[i];
+			int total = m + topk_n;
+			__syncthreads();
+			int new_n;
+			block_select_topk(buf, total, topk, (int)k, &new_n);
+			if (threadIdx.x == 0) {
+				topk_n = new_n;
+				if (new_n >= (int)k) {
+					kth_key = topk[k - 1].key;
+					kth_row = topk[k - 1].row;
+				}
+				cnt = 0;
+			}
+		}
+		__syncthreads();
+	}
+
+	// write block winners (pad with +inf)
+	if (threadIdx.x < MAX_K && threadIdx.x < k) {
+		Cand c;
+		if ((int)threadIdx.x < topk_n) {
+			c.dist = topk[threadIdx.x].dist;
+			c.id = ids[topk[threadIdx.x].row];
+		} else {
+			c.dist = __longlong_as_double(0x7FF0000000000000LL); // +inf
+			c.id = ~0ULL;
+		}
+		block_out[(uint64_t)blockIdx.x * k + threadIdx.x] = c;
+	}
+}
+
+// Row-list path: the exact chain on each listed row, one workgroup per row
+// (grid-stride over cnt <= PF_CAND_CAP rows). All lanes fetch the row's d
+// strided f32 elements into LDS. Cosine then runs the op sequence of
+// k_pf_rescore (lane j owns partial sum j, lane 0 combines in the chain's
+// order and runs the tail); euclidean runs the sequential chain of k_scan<1>
+// / k_gather_dist<1> on lane 0. A single-block k_merge over out[0..cnt)
+// selects the top-k.
+template <int METRIC>
+__global__ __launch_bounds__(64) void k_rows_exact(
+    const float *__restrict__ cm, const double *__restrict__ norms,
+    const uint64_t *__restrict__ ids, uint64_t n_pad, uint32_t d,
+    const float *__restrict__ qg, double q_norm,
+    const uint32_t *__restrict__ rows, uint32_t cnt, Cand *__restrict__ out) {
+	__shared__ float qs[MAX_D];
+	__shared__ float xs[MAX_D];
+	__shared__ float ps[8];
+	for (uint32_t i = threadIdx.x; i < d; i += 64)
+		qs[i] = qg[i];
+	for (uint32_t c = blockIdx.x; c < cnt; c += gridDim.x) {
+		__syncthreads();
+		const uint32_t r = rows[c];
+		for (uint32_t i = threadIdx.x; i < d; i += 64)
+			xs[i] = cm[(uint64_t)i * n_pad + r];
+		__syncthreads();
+		if (METRIC == 0) {
+			const uint32_t d8 = d & ~7u;
+			if (threadIdx.x < 8) {
+				float pj = 0.f;
+				for (uint32_t i = threadIdx.x; i < d8; i += 8)
+					pj = __fadd_rn(pj, __fmul_rn(xs[i], qs[i]));
+				ps[threadIdx.x] = pj;
+			}
+			__syncthreads();
+			if (threadIdx.x == 0) {
+				float p[8];
+#pragma unroll
+				for (int j = 0; j < 8; j++)
+					p[j] = ps[j];
+				uint32_t k8 = d8;
+				float sum = 0.f;
+				sum = __fadd_rn(sum, __fadd_rn(p[0], p[4]));
+				sum = __fadd_rn(sum, __fadd_rn(p[1], p[5]));
+				sum = __fadd_rn(sum, __fadd_rn(p[2], p[6]));
+				sum = __fadd_rn(sum, __fadd_rn(p[3], p[7]));
+				for (; k8 < d; k8++)
+					sum = __fadd_rn(sum, __fmul_rn(xs[k8], qs[k8]));
+				double den = q_norm * norms[r];
+				Cand o;
+				o.dist = 1.0 - (double)sum / den;
+				o.id = ids[r];
+				out[c] = o;
+			}
+		} else {
+			if (threadIdx.x == 0) {
+				float acc = 0.f;
+				for (uint32_t kk = 0; kk < d; kk++) {
+					float diff = xs[kk] - qs[kk];
+					acc = __fadd_rn(acc, __fmul_rn(diff, diff));
+				}
+				Cand o;
+				o.dist = sqrt((double)acc);
+				o.id = ids[r];
+				out[c] = o;
+			}
+		}
+	}
+}
+
 // All-distance kernel: one lane per row, feature-major coalesced reads.
 // Used for parity dumps, k > MAX_K, and (as the product path proper) the
 // six non-headline metrics — each restating the reference's F32 chain
@@ -2915,6 +3169,14 @@ void sdbv_shutdown(sdbv_ctx *ctx) {
 	                (void *)ctx->bcand_cnt})
 		if (p)
 			(void)hipFree(p);
+	for (void *p : {(void *)ctx->flt_mask, (void *)ctx->flt_rows,
+	                ctx->flt_cands})
+		if (p)
+			(void)hipFree(p);
+	if (ctx->flt_mask_pin)
+		(void)hipHostFree(ctx->flt_mask_pin);
+	if (ctx->flt_rows_pin)
+		(void)hipHostFree(ctx->flt_rows_pin);
 	if (ctx->blas)
 		(void)rocblas_destroy_handle(ctx->blas);
 	(void)hipEventDestroy(ctx->ev0);
@@ -3808,6 +4070,307 @@ int sdbv_knn_bruteforce(sdbv_ctx *ctx, uint64_t table, const float *q,
 	        .count();
 
 	uint32_t m = (uint32_t)(k < t.n ? k : t.n);
+	*out_n = m;
+	for (uint32_t i = 0; i < m; i++) {
+		out_ids[i] = host_out[i].id;
+		out_dists[i] = host_out[i].dist;
+	}
+	return SDBV_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Filtered brute-force KNN
+// ---------------------------------------------------------------------------
+
+// Host-only: count the allowed rows below n and list the first cap of them,
+// ascending. Bits at or past n are ignored; words the caller did not supply
+// count as zero. The filtered call counts rows and builds its row list with
+// this same routine.
+uint64_t sdbv_filter_rows(const uint64_t *allow, uint64_t allow_words,
+                          uint64_t n, uint32_t *out_rows, uint64_t cap) {
+	if (!allow)
+		return 0;
+	uint64_t words = (n + 63) / 64;
+	if (words > allow_words)
+		words = allow_words;
+	if (!out_rows)
+		cap = 0;
+	uint64_t count = 0;
+	for (uint64_t w = 0; w < words; w++) {
+		uint64_t bits = allow[w];
+		if (w == n / 64) // the partial last word: drop its tail
+			bits &= (1ULL << (n & 63)) - 1;
+		if (!bits)
+			continue;
+		const uint64_t pc = (uint64_t)__builtin_popcountll(bits);
+		if (count < cap) {
+			uint64_t at = count;
+			for (uint64_t b = bits; b && at < cap; b &= b - 1)
+				out_rows[at++] =
+				    (uint32_t)(w * 64 + (uint64_t)__builtin_ctzll(b));
+		}
+		count += pc;
+	}
+	return count;
+}
+
+// SDBV_FILTER_ROWLIST_MAX, read at each call: the largest allowed-row count
+// the row-list path serves. Default and ceiling PF_CAND_CAP; 0 sends every
+// filtered call to the masked scan.
+static uint64_t filter_rowlist_max() {
+	uint64_t cap = PF_CAND_CAP;
+	const char *e = getenv("SDBV_FILTER_ROWLIST_MAX");
+	if (e && *e) {
+		uint64_t v = strtoull(e, nullptr, 10);
+		if (v < cap)
+			cap = v;
+	}
+	return cap;
+}
+
+// knn_large_k under a filter: the same all-distances launch, and a host
+// selection that skips the rows the bitmap does not allow. Caller holds
+// ctx->mu and has validated allow (ceil(n / 64) words).
+static int knn_large_k_filtered(sdbv_ctx *ctx, Table &t, const float *q,
+                                uint32_t d, uint32_t k, const uint64_t *allow,
+                                uint64_t *out_ids, double *out_dists,
+                                uint32_t *out_n) {
+	int rc = ensure_query_scratch(ctx, d, 1, 1);
+	if (rc != SDBV_OK)
+		return rc;
+	std::memcpy(ctx->q_pin, q, d * sizeof(float)); // pinned staging
+	HIP_CHECK(ctx, hipMemcpyAsync(ctx->q_dev, ctx->q_pin, d * sizeof(float),
+	                              hipMemcpyHostToDevice, ctx->stream));
+	double *dout = nullptr;
+	HIP_CHECK(ctx, hipMalloc(&dout, t.n * sizeof(double)));
+	HIP_CHECK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+	launch_all_dists(ctx, t, q, dout);
+	HIP_CHECK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+	std::vector<double> hd(t.n);
+	std::vector<uint64_t> hids(t.n);
+	if (hipMemcpyAsync(hd.data(), dout, t.n * sizeof(double),
+	                   hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+	    hipMemcpyAsync(hids.data(), t.ids_dev, t.n * sizeof(uint64_t),
+	                   hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+	    hipStreamSynchronize(ctx->stream) != hipSuccess ||
+	    hipGetLastError() != hipSuccess) {
+		(void)hipFree(dout);
+		ctx->err = "knn_large_k_filtered: device error";
+		return SDBV_ERR_HIP;
+	}
+	(void)hipFree(dout);
+	float ms = 0;
+	(void)hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1);
+	ctx->stats.last_scan_kernel_ms = ms;
+	ctx->stats.last_merge_kernel_ms = 0;
+	// bounded max-heap of (total_key(dist), row) over the allowed rows
+	auto tkey = [](double x) {
+		uint64_t bits;
+		std::memcpy(&bits, &x, 8);
+		return (bits >> 63) ? ~bits : (bits | 0x8000000000000000ULL);
+	};
+	std::priority_queue<std::pair<uint64_t, uint64_t>> heap;
+	for (uint64_t r = 0; r < t.n; r++) {
+		if (!((allow[r >> 6] >> (r & 63)) & 1ULL))
+			continue;
+		std::pair<uint64_t, uint64_t> e{tkey(hd[r]), r};
+		if (heap.size() < k) {
+			heap.push(e);
+		} else if (e < heap.top()) {
+			heap.pop();
+			heap.push(e);
+		}
+	}
+	uint32_t m = (uint32_t)heap.size();
+	*out_n = m;
+	for (uint32_t i = m; i-- > 0;) {
+		auto e = heap.top();
+		heap.pop();
+		out_ids[i] = hids[e.second];
+		out_dists[i] = hd[e.second];
+	}
+	return SDBV_OK;
+}
+
+// The k_merge tree over nblocks * k block winners, as knn_exact_scan runs it.
+static void launch_merge_tree(sdbv_ctx *ctx, uint64_t nblocks, uint32_t k) {
+	uint64_t total = nblocks * k;
+	const uint64_t G = 32; // level-1 fan-in
+	if (total > 4096 && nblocks > G) {
+		uint64_t per = ((nblocks + G - 1) / G) * k;
+		hipLaunchKernelGGL(k_merge, dim3((uint32_t)G), dim3(THREADS), 0,
+		                   ctx->stream, (Cand *)ctx->block_out, total, k, per,
+		                   (Cand *)ctx->merge_tmp);
+		hipLaunchKernelGGL(k_merge, dim3(1), dim3(THREADS), 0, ctx->stream,
+		                   (Cand *)ctx->merge_tmp, G * k, k, G * k,
+		                   (Cand *)ctx->final_out);
+	} else {
+		hipLaunchKernelGGL(k_merge, dim3(1), dim3(THREADS), 0, ctx->stream,
+		                   (Cand *)ctx->block_out, total, k, total,
+		                   (Cand *)ctx->final_out);
+	}
+}
+
+// Masked scan of the filtered call: upload the bitmap (tail cleared,
+// zero-filled to n_pad / 64 words), k_scan_masked over k_scan's grid, the
+// merge tree. q already in ctx->q_dev, scratch sized for nblocks. Caller
+// holds ctx->mu.
+static int knn_masked_scan(sdbv_ctx *ctx, Table &t, uint32_t k, double q_norm,
+                           const uint64_t *allow, uint64_t allow_words,
+                           uint64_t nblocks, uint64_t rows_per_block,
+                           Cand *host_out) {
+	const uint64_t mwords = t.n_pad / 64;
+	if (ctx->flt_mask_cap < mwords) {
+		if (ctx->flt_mask)
+			(void)hipFree(ctx->flt_mask);
+		if (ctx->flt_mask_pin)
+			(void)hipHostFree(ctx->flt_mask_pin);
+		ctx->flt_mask = nullptr;
+		ctx->flt_mask_pin = nullptr;
+		ctx->flt_mask_cap = 0;
+		HIP_CHECK(ctx, hipMalloc(&ctx->flt_mask, mwords * sizeof(uint64_t)));
+		HIP_CHECK(ctx,
+		          hipHostMalloc(&ctx->flt_mask_pin, mwords * sizeof(uint64_t)));
+		ctx->flt_mask_cap = mwords;
+	}
+	std::memcpy(ctx->flt_mask_pin, allow, allow_words * sizeof(uint64_t));
+	if (t.n & 63)
+		ctx->flt_mask_pin[allow_words - 1] &= (1ULL << (t.n & 63)) - 1;
+	std::memset(ctx->flt_mask_pin + allow_words, 0,
+	            (mwords - allow_words) * sizeof(uint64_t));
+	HIP_CHECK(ctx, hipMemcpyAsync(ctx->flt_mask, ctx->flt_mask_pin,
+	                              mwords * sizeof(uint64_t),
+	                              hipMemcpyHostToDevice, ctx->stream));
+	HIP_CHECK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+	if (t.metric == SDBV_METRIC_COSINE)
+		hipLaunchKernelGGL(k_scan_masked<0>, dim3((uint32_t)nblocks),
+		                   dim3(THREADS), 0, ctx->stream, t.cm, t.norms, t.n,
+		                   t.n_pad, t.d, ctx->q_dev, q_norm, k, rows_per_block,
+		                   (Cand *)ctx->block_out, t.ids_dev, ctx->flt_mask);
+	else
+		hipLaunchKernelGGL(k_scan_masked<1>, dim3((uint32_t)nblocks),
+		                   dim3(THREADS), 0, ctx->stream, t.cm, t.norms, t.n,
+		                   t.n_pad, t.d, ctx->q_dev, q_norm, k, rows_per_block,
+		                   (Cand *)ctx->block_out, t.ids_dev, ctx->flt_mask);
+	HIP_CHECK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+	launch_merge_tree(ctx, nblocks, k);
+	HIP_CHECK(ctx, hipEventRecord(ctx->ev2, ctx->stream));
+	HIP_CHECK(ctx, hipMemcpyAsync(host_out, ctx->final_out, k * sizeof(Cand),
+	                              hipMemcpyDeviceToHost, ctx->stream));
+	HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+	HIP_CHECK(ctx, hipGetLastError());
+	return SDBV_OK;
+}
+
+// Row-list path of the filtered call: upload the count allowed rows the host
+// listed in ctx->flt_rows_pin, k_rows_exact on them, one single-block
+// k_merge. q already in ctx->q_dev. Caller holds ctx->mu.
+static int knn_row_list(sdbv_ctx *ctx, Table &t, uint32_t k, double q_norm,
+                        uint32_t count, Cand *host_out) {
+	if (!ctx->flt_rows)
+		HIP_CHECK(ctx,
+		          hipMalloc(&ctx->flt_rows, PF_CAND_CAP * sizeof(uint32_t)));
+	if (!ctx->flt_cands)
+		HIP_CHECK(ctx, hipMalloc(&ctx->flt_cands, PF_CAND_CAP * sizeof(Cand)));
+	HIP_CHECK(ctx, hipMemcpyAsync(ctx->flt_rows, ctx->flt_rows_pin,
+	                              count * sizeof(uint32_t),
+	                              hipMemcpyHostToDevice, ctx->stream));
+	const uint32_t nb = count < PF_RESCORE_BLOCKS ? count : PF_RESCORE_BLOCKS;
+	HIP_CHECK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+	if (t.metric == SDBV_METRIC_COSINE)
+		hipLaunchKernelGGL(k_rows_exact<0>, dim3(nb), dim3(64), 0, ctx->stream,
+		                   t.cm, t.norms, t.ids_dev, t.n_pad, t.d, ctx->q_dev,
+		                   q_norm, ctx->flt_rows, count,
+		                   (Cand *)ctx->flt_cands);
+	else
+		hipLaunchKernelGGL(k_rows_exact<1>, dim3(nb), dim3(64), 0, ctx->stream,
+		                   t.cm, t.norms, t.ids_dev, t.n_pad, t.d, ctx->q_dev,
+		                   q_norm, ctx->flt_rows, count,
+		                   (Cand *)ctx->flt_cands);
+	HIP_CHECK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+	hipLaunchKernelGGL(k_merge, dim3(1), dim3(THREADS), 0, ctx->stream,
+	                   (Cand *)ctx->flt_cands, (uint64_t)count, k,
+	                   (uint64_t)count, (Cand *)ctx->final_out);
+	HIP_CHECK(ctx, hipEventRecord(ctx->ev2, ctx->stream));
+	HIP_CHECK(ctx, hipMemcpyAsync(host_out, ctx->final_out, k * sizeof(Cand),
+	                              hipMemcpyDeviceToHost, ctx->stream));
+	HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+	HIP_CHECK(ctx, hipGetLastError());
+	return SDBV_OK;
+}
+
+int sdbv_knn_bruteforce_filtered(sdbv_ctx *ctx, uint64_t table, const float *q,
+                                 uint32_t d, uint32_t k, const uint64_t *allow,
+                                 uint64_t allow_words, uint64_t *out_ids,
+                                 double *out_dists, uint32_t *out_n) {
+	std::lock_guard<std::mutex> lk(ctx->mu);
+	auto it = ctx->tables.find(table);
+	if (it == ctx->tables.end())
+		return SDBV_ERR_NO_TABLE;
+	Table &t = it->second;
+	if (d != t.d)
+		return SDBV_ERR_BAD_ARG;
+	if (k == 0 || k > (1u << 22))
+		return SDBV_ERR_BAD_ARG;
+	if (!allow || allow_words != (t.n + 63) / 64)
+		return SDBV_ERR_BAD_ARG;
+	auto t_start = std::chrono::steady_clock::now();
+	const bool device_topk = k <= MAX_K && t.metric <= SDBV_METRIC_EUCLIDEAN;
+	const uint64_t list_max = device_topk ? filter_rowlist_max() : 0;
+	if (list_max && !ctx->flt_rows_pin)
+		HIP_CHECK(ctx, hipHostMalloc(&ctx->flt_rows_pin,
+		                             PF_CAND_CAP * sizeof(uint32_t)));
+	const uint64_t count = sdbv_filter_rows(allow, allow_words, t.n,
+	                                        ctx->flt_rows_pin, list_max);
+	ctx->stats.last_scan_path = 0;
+	ctx->stats.last_prefilter_candidates = 0;
+	ctx->stats.last_filter_rows = count;
+	ctx->stats.last_rows_scanned = count;
+	ctx->stats.last_scan_kernel_ms = 0;
+	ctx->stats.last_merge_kernel_ms = 0;
+	ctx->stats.last_total_ms = 0;
+	if (count == 0) { // nothing allowed: no launch
+		*out_n = 0;
+		return SDBV_OK;
+	}
+	if (!device_topk)
+		return knn_large_k_filtered(ctx, t, q, d, k, allow, out_ids, out_dists,
+		                            out_n);
+
+	const bool by_list = count <= list_max;
+	// the masked scan runs on k_scan's grid
+	uint64_t tiles = (t.n + TILE - 1) / TILE;
+	uint64_t nblocks = tiles < 2048 ? tiles : 2048;
+	uint64_t tiles_per_block = (tiles + nblocks - 1) / nblocks;
+	uint64_t rows_per_block = tiles_per_block * TILE;
+	nblocks = (t.n + rows_per_block - 1) / rows_per_block;
+	int rc = ensure_query_scratch(ctx, d, by_list ? 1 : nblocks, k);
+	if (rc != SDBV_OK)
+		return rc;
+	double q_norm = sqrt((double)h_sumsq_f32(q, d));
+	std::memcpy(ctx->q_pin, q, d * sizeof(float)); // pinned staging
+	HIP_CHECK(ctx, hipMemcpyAsync(ctx->q_dev, ctx->q_pin, d * sizeof(float),
+	                              hipMemcpyHostToDevice, ctx->stream));
+	Cand host_out[MAX_K];
+	if (by_list)
+		rc = knn_row_list(ctx, t, k, q_norm, (uint32_t)count, host_out);
+	else
+		rc = knn_masked_scan(ctx, t, k, q_norm, allow, allow_words, nblocks,
+		                     rows_per_block, host_out);
+	if (rc != SDBV_OK)
+		return rc;
+	float ms_scan = 0, ms_merge = 0;
+	(void)hipEventElapsedTime(&ms_scan, ctx->ev0, ctx->ev1);
+	(void)hipEventElapsedTime(&ms_merge, ctx->ev1, ctx->ev2);
+	ctx->stats.last_scan_kernel_ms = ms_scan;
+	ctx->stats.last_merge_kernel_ms = ms_merge;
+	ctx->stats.last_scan_path = by_list ? 8u : 7u;
+	ctx->stats.last_total_ms =
+	    std::chrono::duration<double, std::milli>(
+	        std::chrono::steady_clock::now() - t_start)
+	        .count();
+
+	uint32_t m = (uint32_t)(k < count ? k : count);
 	*out_n = m;
 	for (uint32_t i = 0; i < m; i++) {
 		out_ids[i] = host_out[i].id;

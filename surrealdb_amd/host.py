@@ -27,10 +27,15 @@ class KnnTopK:
 
     Results: ascending (distance, id) — identical ordering to the
     reference's (distance, insertion-seq) for monotone ids.
+
+    `row_filter` carries what the reference's planner does to the input
+    stream before the operator sees it (a residual WHERE, deleted records):
+    a bool array over the staged rows, or the ready uint64 bitmap. Only the
+    allowed rows are ranked.
     """
 
     def __init__(self, ctx: Context, table: int, query_vector, k: int,
-                 distance: str = "cosine"):
+                 distance: str = "cosine", row_filter=None):
         from . import METRICS
         if distance not in METRICS:
             raise SdbvError(
@@ -41,9 +46,13 @@ class KnnTopK:
         self.query_vector = np.ascontiguousarray(query_vector, dtype=np.float32)
         self.k = int(k)
         self.distance = distance
+        self.row_filter = row_filter
 
     def execute(self):
         """Consume the staged table; return (ids, dists) ascending."""
+        if self.row_filter is not None:
+            return self.ctx.knn_bruteforce_filtered(
+                self.table, self.query_vector, self.k, self.row_filter)
         return self.ctx.knn_bruteforce(self.table, self.query_vector, self.k)
 
 
