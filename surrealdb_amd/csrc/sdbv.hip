@@ -78,6 +78,34 @@
 		}                                                                      \
 	} while (0)
 
+// Single-query prefilter shadow of a cosine table (optional, at most one tier
+// per table): two device allocations, everything else derived from them.
+//  1 bf16: codes = bf16 of cm, feature-major [d][sn_pad], rounded to
+//    nearest-even; side = pinv, the per-row f32 1/norm (NaN marks a row the
+//    error bound cannot cover).
+//  2 int8: codes = bias-128 bytes, feature-major [d][sn_pad]; side = pscale
+//    (scale/norm per row, NaN marks an uncovered row), then peps, the row's
+//    proven bound.
+//  3 int6: 6-bit codes, bias 32, lane = row, features in groups of 32,
+//    G = ceil(d / 32); codes = plane H [G][sn_pad][4 dwords] with the high
+//    nibbles, then plane L [G][sn_pad][2 dwords] with the low pairs; side =
+//    pscale, peps, then xsum (the row's sum of stored codes).
+struct Shadow {
+	int kind = 0;          // 0 none, 1 bf16, 2 int8, 3 int6
+	void *codes = nullptr; // owning
+	float *side = nullptr; // owning: sn_pad floats per side array
+	uint64_t sn_pad = 0;   // n rounded up to the tier's tile
+	uint64_t bytes = 0;    // both allocations, counted in Table::bytes
+	float *pinv() const { return side; }
+	float *pscale() const { return side; }
+	float *peps() const { return side + sn_pad; }
+	uint32_t *xsum() const { return (uint32_t *)(side + 2 * sn_pad); }
+	uint32_t *plane_h() const { return (uint32_t *)codes; }
+	uint32_t *plane_l(uint32_t d) const {
+		return plane_h() + (uint64_t)((d + 31) / 32) * sn_pad * 4;
+	}
+};
+
 struct Table {
 	uint64_t n = 0;
 	uint64_t n_pad = 0;
@@ -89,28 +117,7 @@ struct Table {
 	float *aux = nullptr;     // per-row f32 selection key aux for the batch
 	                          // path: cosine 1/norm, euclidean sum-of-squares
 	uint64_t *ids_dev = nullptr; // per-row id, device (merge kernel maps)
-	// single-query prefilter (cosine only, optional): bf16 shadow of cm,
-	// feature-major [d][sn_pad], rounded to nearest-even, and the per-row
-	// f32 1/norm (NaN marks a row the error bound cannot cover)
-	uint16_t *shadow = nullptr;
-	float *pinv = nullptr;
-	// or, instead of the bf16 shadow (a table holds at most one): int8
-	// codes, bias-128 bytes, feature-major [d][sn_pad], with per row
-	// pscale = scale/norm (NaN marks an uncovered row) and the row's proven
-	// bound peps; pscale and peps share one allocation
-	uint8_t *shadow8 = nullptr;
-	float *pscale = nullptr;
-	float *peps = nullptr;
-	// or the int6 shadow: 6-bit codes, bias 32, lane = row, features in
-	// groups of 32; plane H [G][sn_pad][4 dwords] holds the high nibbles,
-	// plane L [G][sn_pad][2 dwords] the low pairs (one allocation, L behind
-	// H); pscale, peps and xsum (the row's sum of stored codes) share the
-	// side allocation
-	uint32_t *shadow6 = nullptr;
-	uint32_t *shadow6l = nullptr;
-	uint32_t *xsum = nullptr;
-	uint64_t sn_pad = 0;
-	uint64_t shadow_bytes = 0;
+	Shadow sh;
 	uint64_t bytes = 0;
 };
 
@@ -136,9 +143,8 @@ struct sdbv_ctx {
 	uint32_t *pf_rows = nullptr; // [PF_CAND_CAP] candidate rows
 	void *pf_cands = nullptr;    // [PF_CAND_CAP] rescored Cand
 	void *pf_res = nullptr;      // [MAX_K + 2] Cand: top-k, the count, counter
-	uint64_t pf_slots = 0;       // k_prefilter blocks the device holds at once
-	uint64_t pf8_slots = 0;      // the same for k_prefilter_i8
-	uint64_t pf6_slots = 0;      // the same for k_prefilter_i6
+	uint64_t pf_slots[4] = {};   // by Shadow::kind: blocks of that tier's
+	                             // prefilter kernel the device holds at once
 	// batched path
 	rocblas_handle blas = nullptr;
 	float *S = nullptr; // chunk scores scratch, [chunk][b] col-major
@@ -347,12 +353,54 @@ __device__ static void block_select_topk(LCand *buf, int total, LCand *topk,
 	*out_n = out;
 }
 
-template <int METRIC>
+// The running block top-K of k_scan: prologue and epilogue (the fold between
+// them is written in the kernel). The state lives in the kernel's own
+// __shared__ declarations and is passed in, so the helpers add no LDS.
+// Prologue: thread 0 clears it; the barrier also publishes the LDS query.
+__device__ __forceinline__ static void scan_topk_init(int &cnt, int &topk_n,
+                                                      uint64_t &kth_key,
+                                                      uint32_t &kth_row) {
+	if (threadIdx.x == 0) {
+		cnt = 0;
+		topk_n = 0;
+		kth_key = ~0ULL;
+		kth_row = ~0u;
+	}
+	__syncthreads();
+}
+
+// Epilogue: block winners as Cand{dist, id} (pad with +inf) for k_merge.
+__device__ __forceinline__ static void scan_topk_write(
+    const LCand *topk, int topk_n, uint32_t k,
+    const uint64_t *__restrict__ ids, Cand *__restrict__ block_out) {
+	if (threadIdx.x < MAX_K && threadIdx.x < k) {
+		Cand c;
+		if ((int)threadIdx.x < topk_n) {
+			c.dist = topk[threadIdx.x].dist;
+			c.id = ids[topk[threadIdx.x].row];
+		} else {
+			c.dist = __longlong_as_double(0x7FF0000000000000LL); // +inf
+			c.id = ~0ULL;
+		}
+		block_out[(uint64_t)blockIdx.x * k + threadIdx.x] = c;
+	}
+}
+
+// MASKED (the filtered call) gives a row one more reason to
+// be invalid. mask holds n_pad / 64 words with no bit set at or past n (the
+// host clears the tail and zero-fills behind it). A lane's ROWS_PER_LANE rows
+// start at a multiple of 4, so their bits are one nibble of one word; a wave
+// covers 256 consecutive rows = four words, and when none of its lanes has a
+// live row the wave skips the feature loop: no corpus loads, no arithmetic.
+// The branch is wave-uniform (a ballot) and encloses only the feature loop,
+// never a __syncthreads(). Without MASKED, mask is never read (nullptr).
+template <int METRIC, bool MASKED>
 __global__ __launch_bounds__(THREADS) void k_scan(
     const float *__restrict__ cm, const double *__restrict__ norms,
     uint64_t n, uint64_t n_pad, uint32_t d, const float *__restrict__ qg,
     double q_norm, uint32_t k, uint64_t rows_per_block,
-    Cand *__restrict__ block_out, const uint64_t *__restrict__ ids) {
+    Cand *__restrict__ block_out, const uint64_t *__restrict__ ids,
+    const uint64_t *__restrict__ mask) {
 	__shared__ float qs[MAX_D];
 	__shared__ LCand buf[TILE + MAX_K];
 	__shared__ LCand topk[MAX_K];
@@ -363,13 +411,7 @@ __global__ __launch_bounds__(THREADS) void k_scan(
 
 	for (uint32_t i = threadIdx.x; i < d; i += THREADS)
 		qs[i] = qg[i];
-	if (threadIdx.x == 0) {
-		cnt = 0;
-		topk_n = 0;
-		kth_key = ~0ULL;
-		kth_row = ~0u;
-	}
-	__syncthreads();
+	scan_topk_init(cnt, topk_n, kth_key, kth_row);
 
 	uint64_t row_begin = (uint64_t)blockIdx.x * rows_per_block;
 	uint64_t row_end = row_begin + rows_per_block;
@@ -380,67 +422,88 @@ __global__ __launch_bounds__(THREADS) void k_scan(
 		uint64_t r0 = tile_base + (uint64_t)threadIdx.x * ROWS_PER_LANE;
 		double dist[ROWS_PER_LANE];
 		bool valid[ROWS_PER_LANE];
+		bool live = true;
+		if constexpr (MASKED) {
+			// r0 < n_pad: tile_base is a multiple of TILE below n <= n_pad
+			const uint32_t nib = (uint32_t)(mask[r0 >> 6] >> (r0 & 63)) & 0xFu;
+			bool any = false;
 #pragma unroll
-		for (int c = 0; c < ROWS_PER_LANE; c++)
-			valid[c] = (r0 + c) < row_end;
-
-		if (METRIC == 0) {
-			// cosine: ndarray unrolled_dot restatement, per row (float4 = 4 rows)
-			float4 p[8];
-#pragma unroll
-			for (int j = 0; j < 8; j++)
-				p[j] = make_float4(0.f, 0.f, 0.f, 0.f);
-			uint32_t k8 = 0;
-			for (; k8 + 8 <= d; k8 += 8) {
-#pragma unroll
-				for (uint32_t j = 0; j < 8; j++) {
-					const float4 v =
-					    *(const float4 *)(cm + (uint64_t)(k8 + j) * n_pad + r0);
-					const float qk = qs[k8 + j];
-					p[j].x = __fadd_rn(p[j].x, __fmul_rn(v.x, qk));
-					p[j].y = __fadd_rn(p[j].y, __fmul_rn(v.y, qk));
-					p[j].z = __fadd_rn(p[j].z, __fmul_rn(v.z, qk));
-					p[j].w = __fadd_rn(p[j].w, __fmul_rn(v.w, qk));
-				}
+			for (int c = 0; c < ROWS_PER_LANE; c++) {
+				valid[c] = (r0 + c) < row_end && ((nib >> c) & 1u);
+				any = any || valid[c];
+				dist[c] = 0.0;
 			}
-			float4 sum = make_float4(0.f, 0.f, 0.f, 0.f);
+			live = __ballot(any) != 0ULL;
+		} else {
+#pragma unroll
+			for (int c = 0; c < ROWS_PER_LANE; c++)
+				valid[c] = (r0 + c) < row_end;
+		}
+
+		if (live) {
+			if (METRIC == 0) {
+				// cosine: ndarray unrolled_dot restatement, per row (float4 =
+				// 4 rows)
+				float4 p[8];
+#pragma unroll
+				for (int j = 0; j < 8; j++)
+					p[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+				uint32_t k8 = 0;
+				for (; k8 + 8 <= d; k8 += 8) {
+#pragma unroll
+					for (uint32_t j = 0; j < 8; j++) {
+						const float4 v = *(const float4 *)(cm +
+						    (uint64_t)(k8 + j) * n_pad + r0);
+						const float qk = qs[k8 + j];
+						p[j].x = __fadd_rn(p[j].x, __fmul_rn(v.x, qk));
+						p[j].y = __fadd_rn(p[j].y, __fmul_rn(v.y, qk));
+						p[j].z = __fadd_rn(p[j].z, __fmul_rn(v.z, qk));
+						p[j].w = __fadd_rn(p[j].w, __fmul_rn(v.w, qk));
+					}
+				}
+				float4 sum = make_float4(0.f, 0.f, 0.f, 0.f);
 #define COMB(f)                                                                 \
 	sum.f = __fadd_rn(sum.f, __fadd_rn(p[0].f, p[4].f));                        \
 	sum.f = __fadd_rn(sum.f, __fadd_rn(p[1].f, p[5].f));                        \
 	sum.f = __fadd_rn(sum.f, __fadd_rn(p[2].f, p[6].f));                        \
 	sum.f = __fadd_rn(sum.f, __fadd_rn(p[3].f, p[7].f));
-			COMB(x) COMB(y) COMB(z) COMB(w)
+				COMB(x) COMB(y) COMB(z) COMB(w)
 #undef COMB
-			for (; k8 < d; k8++) {
-				const float4 v = *(const float4 *)(cm + (uint64_t)k8 * n_pad + r0);
-				const float qk = qs[k8];
-				sum.x = __fadd_rn(sum.x, __fmul_rn(v.x, qk));
-				sum.y = __fadd_rn(sum.y, __fmul_rn(v.y, qk));
-				sum.z = __fadd_rn(sum.z, __fmul_rn(v.z, qk));
-				sum.w = __fadd_rn(sum.w, __fmul_rn(v.w, qk));
-			}
-			const float s[4] = {sum.x, sum.y, sum.z, sum.w};
+				for (; k8 < d; k8++) {
+					const float4 v =
+					    *(const float4 *)(cm + (uint64_t)k8 * n_pad + r0);
+					const float qk = qs[k8];
+					sum.x = __fadd_rn(sum.x, __fmul_rn(v.x, qk));
+					sum.y = __fadd_rn(sum.y, __fmul_rn(v.y, qk));
+					sum.z = __fadd_rn(sum.z, __fmul_rn(v.z, qk));
+					sum.w = __fadd_rn(sum.w, __fmul_rn(v.w, qk));
+				}
+				const float s[4] = {sum.x, sum.y, sum.z, sum.w};
 #pragma unroll
-			for (int c = 0; c < ROWS_PER_LANE; c++) {
-				double den = q_norm * norms[r0 + c < n_pad ? r0 + c : 0];
-				dist[c] = 1.0 - (double)s[c] / den;
-			}
-		} else {
-			// euclidean: ndarray-stats sq_l2_dist — sequential f32 chain per row
-			float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-			for (uint32_t kk = 0; kk < d; kk++) {
-				const float4 v = *(const float4 *)(cm + (uint64_t)kk * n_pad + r0);
-				const float qk = qs[kk];
-				float dx = v.x - qk, dy = v.y - qk, dz = v.z - qk, dw = v.w - qk;
-				acc.x = __fadd_rn(acc.x, __fmul_rn(dx, dx));
-				acc.y = __fadd_rn(acc.y, __fmul_rn(dy, dy));
-				acc.z = __fadd_rn(acc.z, __fmul_rn(dz, dz));
-				acc.w = __fadd_rn(acc.w, __fmul_rn(dw, dw));
-			}
-			const float s[4] = {acc.x, acc.y, acc.z, acc.w};
+				for (int c = 0; c < ROWS_PER_LANE; c++) {
+					double den = q_norm * norms[r0 + c < n_pad ? r0 + c : 0];
+					dist[c] = 1.0 - (double)s[c] / den;
+				}
+			} else {
+				// euclidean: ndarray-stats sq_l2_dist — sequential f32 chain
+				// per row
+				float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+				for (uint32_t kk = 0; kk < d; kk++) {
+					const float4 v =
+					    *(const float4 *)(cm + (uint64_t)kk * n_pad + r0);
+					const float qk = qs[kk];
+					float dx = v.x - qk, dy = v.y - qk, dz = v.z - qk,
+					      dw = v.w - qk;
+					acc.x = __fadd_rn(acc.x, __fmul_rn(dx, dx));
+					acc.y = __fadd_rn(acc.y, __fmul_rn(dy, dy));
+					acc.z = __fadd_rn(acc.z, __fmul_rn(dz, dz));
+					acc.w = __fadd_rn(acc.w, __fmul_rn(dw, dw));
+				}
+				const float s[4] = {acc.x, acc.y, acc.z, acc.w};
 #pragma unroll
-			for (int c = 0; c < ROWS_PER_LANE; c++)
-				dist[c] = sqrt((double)s[c]);
+				for (int c = 0; c < ROWS_PER_LANE; c++)
+					dist[c] = sqrt((double)s[c]);
+			}
 		}
 
 		// threshold check + candidate append (rare path)
@@ -452,7 +515,7 @@ __global__ __launch_bounds__(THREADS) void k_scan(
 			if (!valid[c])
 				continue;
 			uint64_t key = d_total_key(dist[c]);
-			uint32_t row32 = (uint32_t)(r0 + c - 0); // row index within shard
+			uint32_t row32 = (uint32_t)(r0 + c); // row index within shard
 			bool take = !full || key < kk_key || (key == kk_key && row32 < kk_row);
 			if (take) {
 				int idx = atomicAdd(&cnt, 1);
@@ -463,7 +526,10 @@ __global__ __launch_bounds__(THREADS) void k_scan(
 		}
 		__syncthreads();
 
-		// merge: all threads select new top-k from {candidates, current topk}
+		// fold: all threads select the new top-k from {candidates, current
+		// topk}. The LCand twin of pf_topk_fold, written here: k_scan is its
+		// one user, and as a helper it costs k_scan<0, false> two VGPRs
+		// (profiles/scan_refactor.md).
 		if (cnt > 0) {
 			int m = cnt;
 			for (int i = threadIdx.x; i < topk_n; i += THREADS)
@@ -484,18 +550,7 @@ __global__ __launch_bounds__(THREADS) void k_scan(
 		__syncthreads();
 	}
 
-	// write block winners (pad with +inf)
-	if (threadIdx.x < MAX_K && threadIdx.x < k) {
-		Cand c;
-		if ((int)threadIdx.x < topk_n) {
-			c.dist = topk[threadIdx.x].dist;
-			c.id = ids[topk[threadIdx.x].row];
-		} else {
-			c.dist = __longlong_as_double(0x7FF0000000000000LL); // +inf
-			c.id = ~0ULL;
-		}
-		block_out[(uint64_t)blockIdx.x * k + threadIdx.x] = c;
-	}
+	scan_topk_write(topk, topk_n, k, ids, block_out);
 }
 
 // Final merge: one block selects global top-k from nblocks*k candidates.
@@ -591,7 +646,7 @@ __global__ __launch_bounds__(THREADS) void k_merge(
 // Single-query cosine prefilter: stream a bf16 shadow of the corpus (half the
 // bytes of the f32 store), keep every row whose approximate distance could
 // reach the top K under the proven bound pf_eps(d), and recompute only those
-// rows with the exact restated chain. Results are bit-identical to k_scan<0>
+// rows with the exact restated chain. Results are bit-identical to k_scan<0, .>
 // by construction: the approximate scores only decide WHICH rows get the
 // exact chain, never a result value or an order.
 // ---------------------------------------------------------------------------
@@ -614,7 +669,7 @@ __host__ __device__ static inline uint32_t pf_bf16_bits(uint32_t u) {
 }
 
 // Bound on |exact - approx| for a row and a query inside the norm window,
-// exact = the restated f32 chain with its f64 finish (k_scan<0>),
+// exact = the restated f32 chain with its f64 finish (k_scan<0, .>),
 // approx = 1 - s~ * inv_q * inv_i in f32 over the bf16 shadow (k_prefilter).
 // In cosine units, i.e. divided by |x||q|, with u = 2^-24:
 //  - quantisation: bf16 keeps 8 significant bits, so round-to-nearest moves
@@ -747,6 +802,65 @@ __device__ static void pf_block_select(uint64_t *buf, int total,
 	*out_n = out;
 }
 
+// The running block top-K of the three prefilter kernels, on packed keys:
+// prologue, fold and epilogue, the packed-u64 twins of k_scan's, with the
+// state in each kernel's own __shared__ declarations. Block 0's prologue
+// also clears the candidate counter for k_pf_compact. Fold, once every
+// thread has appended its survivors to buf[0..cnt) (at most PF_TILE of them
+// into buf[PF_TILE + MAX_K]): if there are any, all threads select the new
+// top-k from {candidates, current topk} and thread 0 moves the threshold.
+__device__ __forceinline__ static void pf_topk_init(
+    int &cnt, int &topk_n, uint64_t &kth, uint32_t *__restrict__ cand_cnt) {
+	if (threadIdx.x == 0) {
+		cnt = 0;
+		topk_n = 0;
+		kth = ~0ULL;
+		if (blockIdx.x == 0)
+			*cand_cnt = 0;
+	}
+	__syncthreads();
+}
+
+__device__ __forceinline__ static void pf_topk_fold(uint64_t *buf,
+                                                    uint64_t *topk, int &cnt,
+                                                    int &topk_n, uint64_t &kth,
+                                                    uint32_t k) {
+	__syncthreads();
+	if (cnt > 0) {
+		int m = cnt;
+		for (int i = threadIdx.x; i < topk_n; i += THREADS)
+			buf[m + i] = topk[i];
+		int total = m + topk_n;
+		__syncthreads();
+		int new_n;
+		pf_block_select(buf, total, topk, (int)k, &new_n);
+		if (threadIdx.x == 0) {
+			topk_n = new_n;
+			if (new_n >= (int)k)
+				kth = topk[k - 1];
+			cnt = 0;
+		}
+	}
+	__syncthreads();
+}
+
+// Block winners as Cand{approximate distance or upper bound, row} (pad with
+// +inf), so that k_merge selects the K smallest of them.
+__device__ __forceinline__ static void pf_topk_write(
+    const uint64_t *topk, int topk_n, uint32_t k, Cand *__restrict__ block_out) {
+	if (threadIdx.x < k) {
+		Cand c;
+		if ((int)threadIdx.x < topk_n) {
+			c.dist = (double)d_unkey32((uint32_t)(topk[threadIdx.x] >> 32));
+			c.id = (uint32_t)topk[threadIdx.x];
+		} else {
+			c.dist = __longlong_as_double(0x7FF0000000000000LL); // +inf
+			c.id = ~0ULL;
+		}
+		block_out[(uint64_t)blockIdx.x * k + threadIdx.x] = c;
+	}
+}
+
 // The k_scan skeleton over the shadow: contiguous row spans per block, 8
 // rows per lane from one 16-byte load per feature, unpack by shift, f32 FMA
 // accumulation, a_i = 1 - s~ * inv_q * inv_i stored to scores[] and fed to
@@ -766,14 +880,7 @@ __global__ __launch_bounds__(THREADS) void k_prefilter(
 	__shared__ int topk_n;
 	__shared__ uint64_t kth;
 
-	if (threadIdx.x == 0) {
-		cnt = 0;
-		topk_n = 0;
-		kth = ~0ULL;
-		if (blockIdx.x == 0)
-			*cand_cnt = 0;
-	}
-	__syncthreads();
+	pf_topk_init(cnt, topk_n, kth, cand_cnt);
 
 	uint64_t row_begin = (uint64_t)blockIdx.x * rows_per_block;
 	uint64_t row_end = row_begin + rows_per_block;
@@ -842,39 +949,10 @@ __global__ __launch_bounds__(THREADS) void k_prefilter(
 				buf[idx] = v;
 			}
 		}
-		__syncthreads();
-
-		if (cnt > 0) {
-			int m = cnt;
-			for (int i = threadIdx.x; i < topk_n; i += THREADS)
-				buf[m + i] = topk[i];
-			int total = m + topk_n;
-			__syncthreads();
-			int new_n;
-			pf_block_select(buf, total, topk, (int)k, &new_n);
-			if (threadIdx.x == 0) {
-				topk_n = new_n;
-				if (new_n >= (int)k)
-					kth = topk[k - 1];
-				cnt = 0;
-			}
-		}
-		__syncthreads();
+		pf_topk_fold(buf, topk, cnt, topk_n, kth, k);
 	}
 
-	// block winners as Cand{approx distance, row} (pad with +inf) so the
-	// existing k_merge selects the K smallest approximate distances
-	if (threadIdx.x < k) {
-		Cand c;
-		if ((int)threadIdx.x < topk_n) {
-			c.dist = (double)d_unkey32((uint32_t)(topk[threadIdx.x] >> 32));
-			c.id = (uint32_t)topk[threadIdx.x];
-		} else {
-			c.dist = __longlong_as_double(0x7FF0000000000000LL); // +inf
-			c.id = ~0ULL;
-		}
-		block_out[(uint64_t)blockIdx.x * k + threadIdx.x] = c;
-	}
+	pf_topk_write(topk, topk_n, k, block_out);
 }
 
 // ---------------------------------------------------------------------------
@@ -897,7 +975,7 @@ __global__ __launch_bounds__(THREADS) void k_prefilter(
 // scale = pscale = NaN and eps = 0: the prefilter always rescores it.
 //
 // Bound on |exact - approx| for a covered row and a query inside the norm
-// window, exact = the restated f32 chain with its f64 finish (k_scan<0>),
+// window, exact = the restated f32 chain with its f64 finish (k_scan<0, .>),
 // approx = 1 - (t - B) * inv_q * pscale in f32 (k_prefilter_i8), where
 // t = the sequential f32 FMA chain over b_k q_k and B = f32(128 sum q_k).
 // In cosine units, i.e. divided by |x||q|, with u = 2^-24:
@@ -1014,14 +1092,7 @@ __global__ __launch_bounds__(THREADS) void k_prefilter_i8(
 	__shared__ int topk_n;
 	__shared__ uint64_t kth;
 
-	if (threadIdx.x == 0) {
-		cnt = 0;
-		topk_n = 0;
-		kth = ~0ULL;
-		if (blockIdx.x == 0)
-			*cand_cnt = 0;
-	}
-	__syncthreads();
+	pf_topk_init(cnt, topk_n, kth, cand_cnt);
 
 	uint64_t row_begin = (uint64_t)blockIdx.x * rows_per_block;
 	uint64_t row_end = row_begin + rows_per_block;
@@ -1107,39 +1178,11 @@ __global__ __launch_bounds__(THREADS) void k_prefilter_i8(
 					buf[idx] = v;
 				}
 			}
-			__syncthreads();
-
-			if (cnt > 0) {
-				int m = cnt;
-				for (int i = threadIdx.x; i < topk_n; i += THREADS)
-					buf[m + i] = topk[i];
-				int total = m + topk_n;
-				__syncthreads();
-				int new_n;
-				pf_block_select(buf, total, topk, (int)k, &new_n);
-				if (threadIdx.x == 0) {
-					topk_n = new_n;
-					if (new_n >= (int)k)
-						kth = topk[k - 1];
-					cnt = 0;
-				}
-			}
-			__syncthreads();
+			pf_topk_fold(buf, topk, cnt, topk_n, kth, k);
 		}
 	}
 
-	// block winners as Cand{upper bound, row} (pad with +inf) for k_merge
-	if (threadIdx.x < k) {
-		Cand c;
-		if ((int)threadIdx.x < topk_n) {
-			c.dist = (double)d_unkey32((uint32_t)(topk[threadIdx.x] >> 32));
-			c.id = (uint32_t)topk[threadIdx.x];
-		} else {
-			c.dist = __longlong_as_double(0x7FF0000000000000LL); // +inf
-			c.id = ~0ULL;
-		}
-		block_out[(uint64_t)blockIdx.x * k + threadIdx.x] = c;
-	}
+	pf_topk_write(topk, topk_n, k, block_out);
 }
 
 // ---------------------------------------------------------------------------
@@ -1185,7 +1228,7 @@ __host__ __device__ static inline float pf_round_up_f32(double e) {
 // pscale = NaN and eps = 0: the prefilter always rescores it.
 //
 // Bound on |exact - approx| for a covered row and a query inside the norm
-// window, exact = the restated f32 chain with its f64 finish (k_scan<0>),
+// window, exact = the restated f32 chain with its f64 finish (k_scan<0, .>),
 // approx = 1 - f32(N) * pscale * qscale in f32 (k_prefilter_i6), where
 // N = sum c_k cq_k as an exact integer, qscale = f32(sq / |q|) and sq the
 // query's scale. In cosine units, i.e. divided by |x||q|, with u = 2^-24,
@@ -1383,14 +1426,7 @@ __global__ __launch_bounds__(THREADS) void k_prefilter_i6(
 	__shared__ int topk_n;
 	__shared__ uint64_t kth;
 
-	if (threadIdx.x == 0) {
-		cnt = 0;
-		topk_n = 0;
-		kth = ~0ULL;
-		if (blockIdx.x == 0)
-			*cand_cnt = 0;
-	}
-	__syncthreads();
+	pf_topk_init(cnt, topk_n, kth, cand_cnt);
 
 	uint64_t row_begin = (uint64_t)blockIdx.x * rows_per_block;
 	uint64_t row_end = row_begin + rows_per_block;
@@ -1468,38 +1504,10 @@ __global__ __launch_bounds__(THREADS) void k_prefilter_i6(
 				}
 			}
 		}
-		__syncthreads();
-
-		if (cnt > 0) {
-			int m = cnt;
-			for (int i = threadIdx.x; i < topk_n; i += THREADS)
-				buf[m + i] = topk[i];
-			int total = m + topk_n;
-			__syncthreads();
-			int new_n;
-			pf_block_select(buf, total, topk, (int)k, &new_n);
-			if (threadIdx.x == 0) {
-				topk_n = new_n;
-				if (new_n >= (int)k)
-					kth = topk[k - 1];
-				cnt = 0;
-			}
-		}
-		__syncthreads();
+		pf_topk_fold(buf, topk, cnt, topk_n, kth, k);
 	}
 
-	// block winners as Cand{upper bound, row} (pad with +inf) for k_merge
-	if (threadIdx.x < k) {
-		Cand c;
-		if ((int)threadIdx.x < topk_n) {
-			c.dist = (double)d_unkey32((uint32_t)(topk[threadIdx.x] >> 32));
-			c.id = (uint32_t)topk[threadIdx.x];
-		} else {
-			c.dist = __longlong_as_double(0x7FF0000000000000LL); // +inf
-			c.id = ~0ULL;
-		}
-		block_out[(uint64_t)blockIdx.x * k + threadIdx.x] = c;
-	}
+	pf_topk_write(topk, topk_n, k, block_out);
 }
 
 // One pass over scores[]: append every row with score <= T_K + 2 eps to the
@@ -1530,273 +1538,21 @@ __global__ void k_pf_compact(const float *__restrict__ scores, uint64_t n,
 	}
 }
 
-// Exact rescore, one workgroup per candidate (grid-stride over the device
-// count): all lanes fetch the row's d strided f32 elements into LDS, then
-// the op sequence of k_scan<0> / k_gather_dist<0> runs on them: 8 partial
-// sums, the same combine, the same tail, the f64 finish with norms[r].
-__global__ __launch_bounds__(64) void k_pf_rescore(
+// The exact chain on listed rows, one 64-lane workgroup per row (grid-stride
+// over cnt rows), out[c] = Cand{dist, ids[rows[c]]}: the body of k_pf_rescore
+// and k_rows_exact. All lanes fetch the row's d strided f32 elements into
+// LDS. Cosine then runs the op sequence of k_scan<0, .> / k_gather_dist<0>: 8
+// partial sums, the same combine, the same tail, the f64 finish with
+// norms[r]. Euclidean runs the sequential chain of k_scan<1, .> /
+// k_gather_dist<1> on lane 0. qs, xs ([MAX_D]) and ps ([8]) are the calling
+// kernel's LDS.
+template <int METRIC>
+__device__ __forceinline__ static void rows_exact(
     const float *__restrict__ cm, const double *__restrict__ norms,
     const uint64_t *__restrict__ ids, uint64_t n_pad, uint32_t d,
     const float *__restrict__ qg, double q_norm,
-    const uint32_t *__restrict__ cand_cnt,
-    const uint32_t *__restrict__ cand_rows, Cand *__restrict__ out) {
-	__shared__ float qs[MAX_D];
-	__shared__ float xs[MAX_D];
-	__shared__ float ps[8];
-	const uint32_t cnt = *cand_cnt;
-	if (cnt > PF_CAND_CAP || blockIdx.x >= cnt)
-		return; // overflow: the host reruns the exact scan
-	for (uint32_t i = threadIdx.x; i < d; i += 64)
-		qs[i] = qg[i];
-	for (uint32_t c = blockIdx.x; c < cnt; c += gridDim.x) {
-		__syncthreads();
-		const uint32_t r = cand_rows[c];
-		for (uint32_t i = threadIdx.x; i < d; i += 64)
-			xs[i] = cm[(uint64_t)i * n_pad + r];
-		__syncthreads();
-		// the chain's 8 partial sums are independent of each other: lane j
-		// runs partial j's own sequence, lane 0 then combines them in the
-		// chain's order — the same operations on the same values
-		const uint32_t d8 = d & ~7u;
-		if (threadIdx.x < 8) {
-			float pj = 0.f;
-			for (uint32_t i = threadIdx.x; i < d8; i += 8)
-				pj = __fadd_rn(pj, __fmul_rn(xs[i], qs[i]));
-			ps[threadIdx.x] = pj;
-		}
-		__syncthreads();
-		if (threadIdx.x == 0) {
-			float p[8];
-#pragma unroll
-			for (int j = 0; j < 8; j++)
-				p[j] = ps[j];
-			uint32_t k8 = d8;
-			float sum = 0.f;
-			sum = __fadd_rn(sum, __fadd_rn(p[0], p[4]));
-			sum = __fadd_rn(sum, __fadd_rn(p[1], p[5]));
-			sum = __fadd_rn(sum, __fadd_rn(p[2], p[6]));
-			sum = __fadd_rn(sum, __fadd_rn(p[3], p[7]));
-			for (; k8 < d; k8++)
-				sum = __fadd_rn(sum, __fmul_rn(xs[k8], qs[k8]));
-			double den = q_norm * norms[r];
-			Cand o;
-			o.dist = 1.0 - (double)sum / den;
-			o.id = ids[r];
-			out[c] = o;
-		}
-	}
-}
-
-// Final select over the rescored candidates: k_merge's (total_cmp dist, id)
-// order with the candidate count read on the device. The raw count lands
-// right behind the k results so one D2H copy carries both; an overflowed
-// count selects nothing (the host reruns the exact scan).
-__global__ __launch_bounds__(THREADS) void k_pf_final(
-    Cand *__restrict__ cands, const uint32_t *__restrict__ cand_cnt,
-    uint32_t k, Cand *__restrict__ out) {
-	const uint32_t raw = *cand_cnt;
-	const uint64_t total = raw > PF_CAND_CAP ? 0 : raw;
-	if (threadIdx.x == 0) {
-		out[k].dist = 0.0;
-		out[k].id = raw;
-	}
-	merge_slice(cands, total, k, total, out);
-}
-
-// ---------------------------------------------------------------------------
-// Filtered brute-force scan (sdbv_knn_bruteforce_filtered):
-// exact top-K over the rows an allowed-row bitmap names. Exact f32 store
-// only, never a shadow.
-// ---------------------------------------------------------------------------
-
-// Masked scan: k_scan with one more reason for a row to be invalid. Same
-// span-per-block grid, LDS query, per-row chains, LCand buffer, select and
-// block_out format, so k_merge finishes it. mask holds n_pad / 64 words with
-// no bit set at or past n (the host clears the tail and zero-fills behind
-// it). A lane's ROWS_PER_LANE rows start at a multiple of 4, so their bits
-// are one nibble of one word; a wave covers 256 consecutive rows = four
-// words, and when none of its lanes has a live row the wave skips the
-// feature loop: no corpus loads, no arithmetic. The branch is wave-uniform
-// (a ballot) and encloses only the feature loop, never a __syncthreads().
-template <int METRIC>
-__global__ __launch_bounds__(THREADS) void k_scan_masked(
-    const float *__restrict__ cm, const double *__restrict__ norms,
-    uint64_t n, uint64_t n_pad, uint32_t d, const float *__restrict__ qg,
-    double q_norm, uint32_t k, uint64_t rows_per_block,
-    Cand *__restrict__ block_out, const uint64_t *__restrict__ ids,
-    const uint64_t *__restrict__ mask) {
-	__shared__ float qs[MAX_D];
-	__shared__ LCand buf[TILE + MAX_K];
-	__shared__ LCand topk[MAX_K];
-	__shared__ int cnt;
-	__shared__ int topk_n;
-	__shared__ uint64_t kth_key;
-	__shared__ uint32_t kth_row;
-
-	for (uint32_t i = threadIdx.x; i < d; i += THREADS)
-		qs[i] = qg[i];
-	if (threadIdx.x == 0) {
-		cnt = 0;
-		topk_n = 0;
-		kth_key = ~0ULL;
-		kth_row = ~0u;
-	}
-	__syncthreads();
-
-	uint64_t row_begin = (uint64_t)blockIdx.x * rows_per_block;
-	uint64_t row_end = row_begin + rows_per_block;
-	if (row_end > n)
-		row_end = n;
-
-	for (uint64_t tile_base = row_begin; tile_base < row_end; tile_base += TILE) {
-		uint64_t r0 = tile_base + (uint64_t)threadIdx.x * ROWS_PER_LANE;
-		// r0 < n_pad: tile_base is a multiple of TILE below n <= n_pad
-		const uint32_t nib = (uint32_t)(mask[r0 >> 6] >> (r0 & 63)) & 0xFu;
-		double dist[ROWS_PER_LANE];
-		bool valid[ROWS_PER_LANE];
-		bool any = false;
-#pragma unroll
-		for (int c = 0; c < ROWS_PER_LANE; c++) {
-			valid[c] = (r0 + c) < row_end && ((nib >> c) & 1u);
-			any = any || valid[c];
-			dist[c] = 0.0;
-		}
-
-		if (__ballot(any) != 0ULL) {
-			if (METRIC == 0) {
-				// cosine: ndarray unrolled_dot restatement, as k_scan<0>
-				float4 p[8];
-#pragma unroll
-				for (int j = 0; j < 8; j++)
-					p[j] = make_float4(0.f, 0.f, 0.f, 0.f);
-				uint32_t k8 = 0;
-				for (; k8 + 8 <= d; k8 += 8) {
-#pragma unroll
-					for (uint32_t j = 0; j < 8; j++) {
-						const float4 v = *(const float4 *)(cm +
-						    (uint64_t)(k8 + j) * n_pad + r0);
-						const float qk = qs[k8 + j];
-						p[j].x = __fadd_rn(p[j].x, __fmul_rn(v.x, qk));
-						p[j].y = __fadd_rn(p[j].y, __fmul_rn(v.y, qk));
-						p[j].z = __fadd_rn(p[j].z, __fmul_rn(v.z, qk));
-						p[j].w = __fadd_rn(p[j].w, __fmul_rn(v.w, qk));
-					}
-				}
-				float4 sum = make_float4(0.f, 0.f, 0.f, 0.f);
-#define COMB(f)                                                                 \
-	sum.f = __fadd_rn(sum.f, __fadd_rn(p[0].f, p[4].f));                        \
-	sum.f = __fadd_rn(sum.f, __fadd_rn(p[1].f, p[5].f));                        \
-	sum.f = __fadd_rn(sum.f, __fadd_rn(p[2].f, p[6].f));                        \
-	sum.f = __fadd_rn(sum.f, __fadd_rn(p[3].f, p[7].f));
-				COMB(x) COMB(y) COMB(z) COMB(w)
-#undef COMB
-				for (; k8 < d; k8++) {
-					const float4 v =
-					    *(const float4 *)(cm + (uint64_t)k8 * n_pad + r0);
-					const float qk = qs[k8];
-					sum.x = __fadd_rn(sum.x, __fmul_rn(v.x, qk));
-					sum.y = __fadd_rn(sum.y, __fmul_rn(v.y, qk));
-					sum.z = __fadd_rn(sum.z, __fmul_rn(v.z, qk));
-					sum.w = __fadd_rn(sum.w, __fmul_rn(v.w, qk));
-				}
-				const float s[4] = {sum.x, sum.y, sum.z, sum.w};
-#pragma unroll
-				for (int c = 0; c < ROWS_PER_LANE; c++) {
-					double den = q_norm * norms[r0 + c < n_pad ? r0 + c : 0];
-					dist[c] = 1.0 - (double)s[c] / den;
-				}
-			} else {
-				// euclidean: the sequential f32 chain, as k_scan<1>
-				float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-				for (uint32_t kk = 0; kk < d; kk++) {
-					const float4 v =
-					    *(const float4 *)(cm + (uint64_t)kk * n_pad + r0);
-					const float qk = qs[kk];
-					float dx = v.x - qk, dy = v.y - qk, dz = v.z - qk,
-					      dw = v.w - qk;
-					acc.x = __fadd_rn(acc.x, __fmul_rn(dx, dx));
-					acc.y = __fadd_rn(acc.y, __fmul_rn(dy, dy));
-					acc.z = __fadd_rn(acc.z, __fmul_rn(dz, dz));
-					acc.w = __fadd_rn(acc.w, __fmul_rn(dw, dw));
-				}
-				const float s[4] = {acc.x, acc.y, acc.z, acc.w};
-#pragma unroll
-				for (int c = 0; c < ROWS_PER_LANE; c++)
-					dist[c] = sqrt((double)s[c]);
-			}
-		}
-
-		// threshold check + candidate append (rare path)
-		uint64_t kk_key = kth_key;
-		uint32_t kk_row = kth_row;
-		int full = (topk_n >= (int)k);
-#pragma unroll
-		for (int c = 0; c < ROWS_PER_LANE; c++) {
-			if (!valid[c])
-				continue;
-			uint64_t key = d_total_key(dist[c]);
-			uint32_t row32 = (uint32_t)(r0 + c);
-			bool take = !full || key < kk_key || (key == kk_key && row32 < kk_row);
-			if (take) {
-				int idx = atomicAdd(&cnt, 1);
-				buf[idx].key = key;
-				buf[idx].dist = dist[c];
-				buf[idx].row = row32;
-			}
-		}
-		__syncthreads();
-
-		// merge: all threads select new top-k from {candidates, current topk}
-		if (cnt > 0) {
-			int m = cnt;
-			for (int i = threadIdx.x; i < topk_n; i += THREADS)
-				buf[m + i] = topk[i];
-			int total = m + topk_n;
-			__syncthreads();
-			int new_n;
-			block_select_topk(buf, total, topk, (int)k, &new_n);
-			if (threadIdx.x == 0) {
-				topk_n = new_n;
-				if (new_n >= (int)k) {
-					kth_key = topk[k - 1].key;
-					kth_row = topk[k - 1].row;
-				}
-				cnt = 0;
-			}
-		}
-		__syncthreads();
-	}
-
-	// write block winners (pad with +inf)
-	if (threadIdx.x < MAX_K && threadIdx.x < k) {
-		Cand c;
-		if ((int)threadIdx.x < topk_n) {
-			c.dist = topk[threadIdx.x].dist;
-			c.id = ids[topk[threadIdx.x].row];
-		} else {
-			c.dist = __longlong_as_double(0x7FF0000000000000LL); // +inf
-			c.id = ~0ULL;
-		}
-		block_out[(uint64_t)blockIdx.x * k + threadIdx.x] = c;
-	}
-}
-
-// Row-list path: the exact chain on each listed row, one workgroup per row
-// (grid-stride over cnt <= PF_CAND_CAP rows). All lanes fetch the row's d
-// strided f32 elements into LDS. Cosine then runs the op sequence of
-// k_pf_rescore (lane j owns partial sum j, lane 0 combines in the chain's
-// order and runs the tail); euclidean runs the sequential chain of k_scan<1>
-// / k_gather_dist<1> on lane 0. A single-block k_merge over out[0..cnt)
-// selects the top-k.
-template <int METRIC>
-__global__ __launch_bounds__(64) void k_rows_exact(
-    const float *__restrict__ cm, const double *__restrict__ norms,
-    const uint64_t *__restrict__ ids, uint64_t n_pad, uint32_t d,
-    const float *__restrict__ qg, double q_norm,
-    const uint32_t *__restrict__ rows, uint32_t cnt, Cand *__restrict__ out) {
-	__shared__ float qs[MAX_D];
-	__shared__ float xs[MAX_D];
-	__shared__ float ps[8];
+    const uint32_t *__restrict__ rows, uint32_t cnt, Cand *__restrict__ out,
+    float *qs, float *xs, float *ps) {
 	for (uint32_t i = threadIdx.x; i < d; i += 64)
 		qs[i] = qg[i];
 	for (uint32_t c = blockIdx.x; c < cnt; c += gridDim.x) {
@@ -1806,6 +1562,9 @@ __global__ __launch_bounds__(64) void k_rows_exact(
 			xs[i] = cm[(uint64_t)i * n_pad + r];
 		__syncthreads();
 		if (METRIC == 0) {
+			// the chain's 8 partial sums are independent of each other: lane
+			// j runs partial j's own sequence, lane 0 then combines them in
+			// the chain's order — the same operations on the same values
 			const uint32_t d8 = d & ~7u;
 			if (threadIdx.x < 8) {
 				float pj = 0.f;
@@ -1847,6 +1606,56 @@ __global__ __launch_bounds__(64) void k_rows_exact(
 			}
 		}
 	}
+}
+
+// Exact rescore of the prefilter's candidates: rows_exact<0> over the count
+// k_pf_compact left on the device.
+__global__ __launch_bounds__(64) void k_pf_rescore(
+    const float *__restrict__ cm, const double *__restrict__ norms,
+    const uint64_t *__restrict__ ids, uint64_t n_pad, uint32_t d,
+    const float *__restrict__ qg, double q_norm,
+    const uint32_t *__restrict__ cand_cnt,
+    const uint32_t *__restrict__ cand_rows, Cand *__restrict__ out) {
+	__shared__ float qs[MAX_D];
+	__shared__ float xs[MAX_D];
+	__shared__ float ps[8];
+	const uint32_t cnt = *cand_cnt;
+	if (cnt > PF_CAND_CAP || blockIdx.x >= cnt)
+		return; // overflow: the host reruns the exact scan
+	rows_exact<0>(cm, norms, ids, n_pad, d, qg, q_norm, cand_rows, cnt, out,
+	              qs, xs, ps);
+}
+
+// Row-list path of the filtered call: rows_exact on the
+// cnt <= PF_CAND_CAP allowed rows the host listed. A single-block k_merge
+// over out[0..cnt) selects the top-k.
+template <int METRIC>
+__global__ __launch_bounds__(64) void k_rows_exact(
+    const float *__restrict__ cm, const double *__restrict__ norms,
+    const uint64_t *__restrict__ ids, uint64_t n_pad, uint32_t d,
+    const float *__restrict__ qg, double q_norm,
+    const uint32_t *__restrict__ rows, uint32_t cnt, Cand *__restrict__ out) {
+	__shared__ float qs[MAX_D];
+	__shared__ float xs[MAX_D];
+	__shared__ float ps[8];
+	rows_exact<METRIC>(cm, norms, ids, n_pad, d, qg, q_norm, rows, cnt, out,
+	                   qs, xs, ps);
+}
+
+// Final select over the rescored candidates: k_merge's (total_cmp dist, id)
+// order with the candidate count read on the device. The raw count lands
+// right behind the k results so one D2H copy carries both; an overflowed
+// count selects nothing (the host reruns the exact scan).
+__global__ __launch_bounds__(THREADS) void k_pf_final(
+    Cand *__restrict__ cands, const uint32_t *__restrict__ cand_cnt,
+    uint32_t k, Cand *__restrict__ out) {
+	const uint32_t raw = *cand_cnt;
+	const uint64_t total = raw > PF_CAND_CAP ? 0 : raw;
+	if (threadIdx.x == 0) {
+		out[k].dist = 0.0;
+		out[k].id = raw;
+	}
+	merge_slice(cands, total, k, total, out);
 }
 
 // All-distance kernel: one lane per row, feature-major coalesced reads.
@@ -3104,16 +2913,10 @@ static void free_table(Table &t) {
 		(void)hipFree(t.aux);
 	if (t.ids_dev)
 		(void)hipFree(t.ids_dev);
-	if (t.shadow)
-		(void)hipFree(t.shadow);
-	if (t.pinv)
-		(void)hipFree(t.pinv);
-	if (t.shadow8)
-		(void)hipFree(t.shadow8);
-	if (t.pscale)
-		(void)hipFree(t.pscale); // peps (and xsum) live in the same allocation
-	if (t.shadow6)
-		(void)hipFree(t.shadow6); // plane L lives in the same allocation
+	if (t.sh.codes)
+		(void)hipFree(t.sh.codes);
+	if (t.sh.side)
+		(void)hipFree(t.sh.side);
 	t = Table{};
 }
 
@@ -3237,198 +3040,131 @@ static void refresh_bytes_staged(sdbv_ctx *ctx) {
 }
 
 static void free_shadow(sdbv_ctx *ctx, Table *t) {
-	if (t->shadow)
-		(void)hipFree(t->shadow);
-	if (t->pinv)
-		(void)hipFree(t->pinv);
-	if (t->shadow8)
-		(void)hipFree(t->shadow8);
-	if (t->pscale)
-		(void)hipFree(t->pscale);
-	if (t->shadow6)
-		(void)hipFree(t->shadow6);
-	t->shadow = nullptr;
-	t->pinv = nullptr;
-	t->shadow8 = nullptr;
-	t->shadow6 = nullptr;
-	t->shadow6l = nullptr;
-	t->xsum = nullptr;
-	t->pscale = nullptr;
-	t->peps = nullptr;
-	t->bytes -= t->shadow_bytes;
-	t->shadow_bytes = 0;
-	t->sn_pad = 0;
+	if (t->sh.codes)
+		(void)hipFree(t->sh.codes);
+	if (t->sh.side)
+		(void)hipFree(t->sh.side);
+	t->bytes -= t->sh.bytes;
+	t->sh = Shadow{};
 	refresh_bytes_staged(ctx);
 }
 
-// Build the prefilter shadow of a staged cosine table (norms already
-// computed, in stream order). +50 % device memory; a failed allocation leaves
-// the table without a shadow and returns SDBV_ERR_OOM.
-static int build_shadow(sdbv_ctx *ctx, Table *t) {
+// What the three shadow tiers differ in, by Shadow::kind: the rows of one
+// block-sweep of the tier's prefilter kernel (sn_pad is a multiple of it),
+// the f32-sized side values per row, and (below) the code bytes.
+struct ShadowTier {
+	uint64_t tile;
+	uint64_t side_per_row;
+};
+static const ShadowTier SHADOW_TIERS[4] = {
+    {0, 0}, {PF_TILE, 1}, {PF8_TILE, 2}, {PF6_TILE, 3}};
+
+// bf16: 2 d bytes per row (+50 % of the f32 store); int8: d (+25 %); int6:
+// 0.75 d_pad, d_pad = d rounded up to a multiple of 32 (planes H and L).
+static uint64_t shadow_code_bytes(int kind, uint32_t d, uint64_t sn_pad) {
+	switch (kind) {
+	case 1: return 2ull * d * sn_pad;
+	case 2: return (uint64_t)d * sn_pad;
+	default: return 24ull * ((d + 31) / 32) * sn_pad;
+	}
+}
+
+// Build the kind shadow of a staged cosine table (norms already computed, in
+// stream order), instead of any other kind the table holds. A failed
+// allocation leaves the table without a shadow and returns SDBV_ERR_OOM.
+static int build_shadow(sdbv_ctx *ctx, Table *t, int kind) {
 	if (t->metric != SDBV_METRIC_COSINE)
 		return SDBV_ERR_UNSUPPORTED;
-	if (t->shadow)
+	if (t->sh.kind == kind)
 		return SDBV_OK;
-	if (t->shadow8 || t->shadow6)
+	if (t->sh.kind)
 		free_shadow(ctx, t);
-	uint64_t sn_pad = ((t->n + PF_TILE - 1) / PF_TILE) * PF_TILE;
-	if (sn_pad == 0)
-		sn_pad = PF_TILE;
-	uint64_t sh_bytes = (uint64_t)t->d * sn_pad * sizeof(uint16_t);
-	uint64_t pi_bytes = sn_pad * sizeof(float);
-	if (hipMalloc(&t->shadow, sh_bytes) != hipSuccess ||
-	    hipMalloc(&t->pinv, pi_bytes) != hipSuccess) {
+	const ShadowTier &tier = SHADOW_TIERS[kind];
+	Shadow sh;
+	sh.sn_pad = ((t->n + tier.tile - 1) / tier.tile) * tier.tile;
+	if (sh.sn_pad == 0)
+		sh.sn_pad = tier.tile;
+	const uint64_t code_bytes = shadow_code_bytes(kind, t->d, sh.sn_pad);
+	const uint64_t side_bytes = tier.side_per_row * sh.sn_pad * sizeof(float);
+	if (hipMalloc(&sh.codes, code_bytes) != hipSuccess ||
+	    hipMalloc(&sh.side, side_bytes) != hipSuccess) {
 		(void)hipGetLastError(); // allocation failure is not sticky
-		if (t->shadow)
-			(void)hipFree(t->shadow);
-		t->shadow = nullptr;
-		t->pinv = nullptr;
+		if (sh.codes)
+			(void)hipFree(sh.codes);
 		return SDBV_ERR_OOM;
 	}
-	t->sn_pad = sn_pad;
-	t->shadow_bytes = sh_bytes + pi_bytes;
-	t->bytes += t->shadow_bytes;
-	uint64_t groups = sn_pad / PF_ROWS_PER_LANE;
-	hipLaunchKernelGGL(k_shadow, dim3((uint32_t)((groups + 255) / 256)),
-	                   dim3(256), 0, ctx->stream, t->cm, t->norms, t->shadow,
-	                   t->pinv, t->n, t->n_pad, sn_pad, t->d);
+	sh.kind = kind;
+	sh.bytes = code_bytes + side_bytes;
+	t->sh = sh;
+	t->bytes += sh.bytes;
+	const uint64_t sn_pad = sh.sn_pad;
+	switch (kind) {
+	case 1: { // one lane per PF_ROWS_PER_LANE rows
+		uint64_t groups = sn_pad / PF_ROWS_PER_LANE;
+		hipLaunchKernelGGL(k_shadow, dim3((uint32_t)((groups + 255) / 256)),
+		                   dim3(256), 0, ctx->stream, t->cm, t->norms,
+		                   (uint16_t *)sh.codes, sh.pinv(), t->n, t->n_pad,
+		                   sn_pad, t->d);
+		break;
+	}
+	case 2: // one lane per row
+		hipLaunchKernelGGL(k_shadow_i8, dim3((uint32_t)(sn_pad / 256)),
+		                   dim3(256), 0, ctx->stream, t->cm, t->norms,
+		                   (uint8_t *)sh.codes, sh.pscale(), sh.peps(), t->n,
+		                   t->n_pad, sn_pad, t->d);
+		break;
+	case 3:
+		hipLaunchKernelGGL(k_shadow_i6, dim3((uint32_t)(sn_pad / 256)),
+		                   dim3(256), 0, ctx->stream, t->cm, t->norms,
+		                   sh.plane_h(), sh.plane_l(t->d), sh.pscale(),
+		                   sh.peps(), sh.xsum(), t->n, t->n_pad, sn_pad, t->d);
+		break;
+	}
 	HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
 	HIP_CHECK(ctx, hipGetLastError());
 	refresh_bytes_staged(ctx);
 	return SDBV_OK;
 }
 
-// The int8 shadow instead: d + 8 bytes per row (+25 %). Same contract.
-static int build_shadow_i8(sdbv_ctx *ctx, Table *t) {
-	if (t->metric != SDBV_METRIC_COSINE)
-		return SDBV_ERR_UNSUPPORTED;
-	if (t->shadow8)
-		return SDBV_OK;
-	if (t->shadow || t->shadow6)
-		free_shadow(ctx, t);
-	uint64_t sn_pad = ((t->n + PF8_TILE - 1) / PF8_TILE) * PF8_TILE;
-	if (sn_pad == 0)
-		sn_pad = PF8_TILE;
-	uint64_t sh_bytes = (uint64_t)t->d * sn_pad;
-	uint64_t side_bytes = 2 * sn_pad * sizeof(float);
-	if (hipMalloc(&t->shadow8, sh_bytes) != hipSuccess ||
-	    hipMalloc(&t->pscale, side_bytes) != hipSuccess) {
-		(void)hipGetLastError(); // allocation failure is not sticky
-		if (t->shadow8)
-			(void)hipFree(t->shadow8);
-		t->shadow8 = nullptr;
-		t->pscale = nullptr;
-		return SDBV_ERR_OOM;
-	}
-	t->peps = t->pscale + sn_pad;
-	t->sn_pad = sn_pad;
-	t->shadow_bytes = sh_bytes + side_bytes;
-	t->bytes += t->shadow_bytes;
-	hipLaunchKernelGGL(k_shadow_i8, dim3((uint32_t)(sn_pad / 256)), dim3(256),
-	                   0, ctx->stream, t->cm, t->norms, t->shadow8, t->pscale,
-	                   t->peps, t->n, t->n_pad, sn_pad, t->d);
-	HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-	HIP_CHECK(ctx, hipGetLastError());
-	refresh_bytes_staged(ctx);
-	return SDBV_OK;
-}
-
-// The int6 shadow instead: 0.75 * d_pad + 12 bytes per row, d_pad = d rounded
-// up to a multiple of 32. Same contract.
-static int build_shadow_i6(sdbv_ctx *ctx, Table *t) {
-	if (t->metric != SDBV_METRIC_COSINE)
-		return SDBV_ERR_UNSUPPORTED;
-	if (t->shadow6)
-		return SDBV_OK;
-	if (t->shadow || t->shadow8)
-		free_shadow(ctx, t);
-	uint64_t sn_pad = ((t->n + PF6_TILE - 1) / PF6_TILE) * PF6_TILE;
-	if (sn_pad == 0)
-		sn_pad = PF6_TILE;
-	const uint64_t G = (t->d + 31) / 32;
-	uint64_t h_bytes = G * sn_pad * 16, l_bytes = G * sn_pad * 8;
-	uint64_t side_bytes = 3 * sn_pad * sizeof(float);
-	if (hipMalloc(&t->shadow6, h_bytes + l_bytes) != hipSuccess ||
-	    hipMalloc(&t->pscale, side_bytes) != hipSuccess) {
-		(void)hipGetLastError(); // allocation failure is not sticky
-		if (t->shadow6)
-			(void)hipFree(t->shadow6);
-		t->shadow6 = nullptr;
-		t->pscale = nullptr;
-		return SDBV_ERR_OOM;
-	}
-	t->shadow6l = t->shadow6 + h_bytes / sizeof(uint32_t);
-	t->peps = t->pscale + sn_pad;
-	t->xsum = (uint32_t *)(t->peps + sn_pad);
-	t->sn_pad = sn_pad;
-	t->shadow_bytes = h_bytes + l_bytes + side_bytes;
-	t->bytes += t->shadow_bytes;
-	hipLaunchKernelGGL(k_shadow_i6, dim3((uint32_t)(sn_pad / 256)), dim3(256),
-	                   0, ctx->stream, t->cm, t->norms, t->shadow6,
-	                   t->shadow6l, t->pscale, t->peps, t->xsum, t->n,
-	                   t->n_pad, sn_pad, t->d);
-	HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-	HIP_CHECK(ctx, hipGetLastError());
-	refresh_bytes_staged(ctx);
-	return SDBV_OK;
-}
-
-// Default minimum row count from which scan staging builds the shadow: the
-// measured crossover (profiles/prefilter_scan.md) below which the extra
-// launches of the prefilter path cost more than the halved stream saves.
+// Default minimum row counts of the staging policy, one measured crossover
+// per tier: a shadow at all, below which the extra launches of the prefilter
+// path cost more than the halved stream saves (profiles/prefilter_scan.md);
+// int8 rather than bf16 (profiles/prefilter_i8.md); int6 rather than int8
+// (profiles/prefilter_i6.md). The last two are never below the first.
 #define PF_DEFAULT_MIN_ROWS 500000ull
-
-// Staging policy: SDBV_SCAN_PREFILTER=0 opts out;
-// SDBV_SCAN_PREFILTER_MIN_ROWS overrides the default minimum row count.
-static bool shadow_policy(const Table *t) {
-	if (t->metric != SDBV_METRIC_COSINE)
-		return false;
-	const char *e = getenv("SDBV_SCAN_PREFILTER");
-	if (e && e[0] == '0' && e[1] == 0)
-		return false;
-	uint64_t min_rows = PF_DEFAULT_MIN_ROWS;
-	const char *m = getenv("SDBV_SCAN_PREFILTER_MIN_ROWS");
-	if (m && *m)
-		min_rows = strtoull(m, nullptr, 10);
-	return t->n >= min_rows;
-}
-
-// Default minimum row count from which the shadow that staging builds is the
-// int8 one: the measured crossover against the bf16 tier
-// (profiles/prefilter_i8.md); never below PF_DEFAULT_MIN_ROWS.
 #define PF8_DEFAULT_MIN_ROWS 500000ull
-
-// Which shadow staging builds once shadow_policy asked for one:
-// SDBV_SCAN_PREFILTER_I8=0 keeps bf16; SDBV_SCAN_PREFILTER_I8_MIN_ROWS
-// overrides the int8 minimum row count (independent of
-// SDBV_SCAN_PREFILTER_MIN_ROWS).
-static bool shadow_policy_i8(const Table *t) {
-	const char *e = getenv("SDBV_SCAN_PREFILTER_I8");
-	if (e && e[0] == '0' && e[1] == 0)
-		return false;
-	uint64_t min_rows = PF8_DEFAULT_MIN_ROWS;
-	const char *m = getenv("SDBV_SCAN_PREFILTER_I8_MIN_ROWS");
-	if (m && *m)
-		min_rows = strtoull(m, nullptr, 10);
-	return t->n >= min_rows;
-}
-
-// Default minimum row count from which the shadow that staging builds is the
-// int6 one, given that the int8 policy holds: the measured crossover against
-// the int8 tier (profiles/prefilter_i6.md); never below PF_DEFAULT_MIN_ROWS.
 #define PF6_DEFAULT_MIN_ROWS 500000ull
 
-// SDBV_SCAN_PREFILTER_I6=0 keeps int8; SDBV_SCAN_PREFILTER_I6_MIN_ROWS
-// overrides the int6 minimum row count (independent of the other two).
-static bool shadow_policy_i6(const Table *t) {
-	const char *e = getenv("SDBV_SCAN_PREFILTER_I6");
+// One staging policy question: env_flag=0 answers no; otherwise the table
+// needs env_min_rows rows (default default_min). The three row counts are
+// independent of each other.
+static bool shadow_policy(const Table *t, const char *env_flag,
+                          const char *env_min_rows, uint64_t default_min) {
+	const char *e = getenv(env_flag);
 	if (e && e[0] == '0' && e[1] == 0)
 		return false;
-	uint64_t min_rows = PF6_DEFAULT_MIN_ROWS;
-	const char *m = getenv("SDBV_SCAN_PREFILTER_I6_MIN_ROWS");
+	uint64_t min_rows = default_min;
+	const char *m = getenv(env_min_rows);
 	if (m && *m)
 		min_rows = strtoull(m, nullptr, 10);
 	return t->n >= min_rows;
+}
+
+// The shadow that scan staging builds: none off cosine or when
+// SDBV_SCAN_PREFILTER says no; else bf16 when SDBV_SCAN_PREFILTER_I8 says
+// no; else int8 when SDBV_SCAN_PREFILTER_I6 says no; else int6.
+static int staged_shadow_kind(const Table *t) {
+	if (t->metric != SDBV_METRIC_COSINE ||
+	    !shadow_policy(t, "SDBV_SCAN_PREFILTER", "SDBV_SCAN_PREFILTER_MIN_ROWS",
+	                   PF_DEFAULT_MIN_ROWS))
+		return 0;
+	if (!shadow_policy(t, "SDBV_SCAN_PREFILTER_I8",
+	                   "SDBV_SCAN_PREFILTER_I8_MIN_ROWS", PF8_DEFAULT_MIN_ROWS))
+		return 1;
+	if (!shadow_policy(t, "SDBV_SCAN_PREFILTER_I6",
+	                   "SDBV_SCAN_PREFILTER_I6_MIN_ROWS", PF6_DEFAULT_MIN_ROWS))
+		return 2;
+	return 3;
 }
 
 static int finish_stage(sdbv_ctx *ctx, Table *t, bool scan_table) {
@@ -3451,10 +3187,9 @@ static int finish_stage(sdbv_ctx *ctx, Table *t, bool scan_table) {
 	refresh_bytes_staged(ctx);
 	// a table staged for scanning gets the prefilter shadow when the policy
 	// asks for one; without the memory for it the table simply has none
-	if (scan_table && shadow_policy(t)) {
-		int rc = !shadow_policy_i8(t)  ? build_shadow(ctx, t)
-		         : shadow_policy_i6(t) ? build_shadow_i6(ctx, t)
-		                               : build_shadow_i8(ctx, t);
+	const int kind = scan_table ? staged_shadow_kind(t) : 0;
+	if (kind) {
+		int rc = build_shadow(ctx, t, kind);
 		if (rc != SDBV_OK && rc != SDBV_ERR_OOM)
 			return rc;
 	}
@@ -3513,10 +3248,19 @@ int sdbv_table_set_prefilter(sdbv_ctx *ctx, uint64_t table, int on) {
 	if (t->metric != SDBV_METRIC_COSINE)
 		return SDBV_ERR_UNSUPPORTED;
 	if (on)
-		return build_shadow(ctx, t);
-	if (t->shadow || t->shadow8 || t->shadow6)
+		return build_shadow(ctx, t, 1);
+	if (t->sh.kind)
 		free_shadow(ctx, t);
 	return SDBV_OK;
+}
+
+// sdbv_table_set_prefilter_kind(.., 2) and sdbv_table_set_prefilter_i6.
+static int set_shadow_kind(sdbv_ctx *ctx, uint64_t table, int kind) {
+	std::lock_guard<std::mutex> lk(ctx->mu);
+	auto it = ctx->tables.find(table);
+	if (it == ctx->tables.end())
+		return SDBV_ERR_NO_TABLE;
+	return build_shadow(ctx, &it->second, kind);
 }
 
 int sdbv_table_set_prefilter_kind(sdbv_ctx *ctx, uint64_t table, int kind) {
@@ -3524,21 +3268,13 @@ int sdbv_table_set_prefilter_kind(sdbv_ctx *ctx, uint64_t table, int kind) {
 		return SDBV_ERR_BAD_ARG;
 	if (kind < 2)
 		return sdbv_table_set_prefilter(ctx, table, kind);
-	std::lock_guard<std::mutex> lk(ctx->mu);
-	auto it = ctx->tables.find(table);
-	if (it == ctx->tables.end())
-		return SDBV_ERR_NO_TABLE;
-	return build_shadow_i8(ctx, &it->second);
+	return set_shadow_kind(ctx, table, 2);
 }
 
 // The int6 shadow has an entry of its own: sdbv_table_set_prefilter_kind
 // keeps rejecting every kind above 2, as its callers rely on.
 int sdbv_table_set_prefilter_i6(sdbv_ctx *ctx, uint64_t table) {
-	std::lock_guard<std::mutex> lk(ctx->mu);
-	auto it = ctx->tables.find(table);
-	if (it == ctx->tables.end())
-		return SDBV_ERR_NO_TABLE;
-	return build_shadow_i6(ctx, &it->second);
+	return set_shadow_kind(ctx, table, 3);
 }
 
 float sdbv_prefilter_eps(uint32_t d) { return pf_eps(d); }
@@ -3673,6 +3409,84 @@ static int ensure_query_scratch(sdbv_ctx *ctx, uint32_t d, uint64_t nblocks,
 	return SDBV_OK;
 }
 
+// Upload the query: q into the pinned staging buffer, then q_bytes of it
+// (the d floats, and whatever the caller put behind them) to ctx->q_dev.
+static int stage_query(sdbv_ctx *ctx, const float *q, uint32_t d,
+                       size_t q_bytes) {
+	std::memcpy(ctx->q_pin, q, d * sizeof(float));
+	HIP_CHECK(ctx, hipMemcpyAsync(ctx->q_dev, ctx->q_pin, q_bytes,
+	                              hipMemcpyHostToDevice, ctx->stream));
+	return SDBV_OK;
+}
+
+// Hand the first m selected candidates to the caller.
+static void copy_results(const Cand *host_out, uint32_t m, uint64_t *out_ids,
+                         double *out_dists, uint32_t *out_n) {
+	*out_n = m;
+	for (uint32_t i = 0; i < m; i++) {
+		out_ids[i] = host_out[i].id;
+		out_dists[i] = host_out[i].dist;
+	}
+}
+
+// Grid of k_scan: contiguous spans of whole tiles per block, at most 2048
+// blocks (enough to fill 256 CUs).
+static uint64_t scan_grid(uint64_t n, uint64_t *rows_per_block) {
+	uint64_t tiles = (n + TILE - 1) / TILE;
+	uint64_t nblocks = tiles < 2048 ? tiles : 2048;
+	if (nblocks == 0)
+		nblocks = 1;
+	uint64_t tiles_per_block = (tiles + nblocks - 1) / nblocks;
+	*rows_per_block = tiles_per_block * TILE;
+	return (n + *rows_per_block - 1) / *rows_per_block;
+}
+
+// Launch k_scan over scan_grid (mask = nullptr: every row below n).
+static void launch_scan(sdbv_ctx *ctx, Table &t, uint32_t k, double q_norm,
+                        uint64_t nblocks, uint64_t rows_per_block,
+                        const uint64_t *mask) {
+#define LAUNCH_SCAN(M, MASKED)                                                 \
+	hipLaunchKernelGGL((k_scan<M, MASKED>), dim3((uint32_t)nblocks),           \
+	                   dim3(THREADS), 0, ctx->stream, t.cm, t.norms, t.n,      \
+	                   t.n_pad, t.d, ctx->q_dev, q_norm, k, rows_per_block,    \
+	                   (Cand *)ctx->block_out, t.ids_dev, mask)
+	const bool cosine = t.metric == SDBV_METRIC_COSINE;
+	if (mask) {
+		if (cosine)
+			LAUNCH_SCAN(0, true);
+		else
+			LAUNCH_SCAN(1, true);
+	} else {
+		if (cosine)
+			LAUNCH_SCAN(0, false);
+		else
+			LAUNCH_SCAN(1, false);
+	}
+#undef LAUNCH_SCAN
+}
+
+// The k_merge tree over the nblocks * k block winners in ctx->block_out:
+// the top-k lands in ctx->final_out. Top-k of per-slice top-ks is the global
+// top-k, exactly.
+static void launch_merge_tree(sdbv_ctx *ctx, uint64_t nblocks, uint32_t k) {
+	uint64_t total = nblocks * k;
+	const uint64_t G = 32; // level-1 fan-in
+	if (total > 4096 && nblocks > G) {
+		// two levels: G slices in parallel, then one block over G * k
+		uint64_t per = ((nblocks + G - 1) / G) * k;
+		hipLaunchKernelGGL(k_merge, dim3((uint32_t)G), dim3(THREADS), 0,
+		                   ctx->stream, (Cand *)ctx->block_out, total, k, per,
+		                   (Cand *)ctx->merge_tmp);
+		hipLaunchKernelGGL(k_merge, dim3(1), dim3(THREADS), 0, ctx->stream,
+		                   (Cand *)ctx->merge_tmp, G * k, k, G * k,
+		                   (Cand *)ctx->final_out);
+	} else {
+		hipLaunchKernelGGL(k_merge, dim3(1), dim3(THREADS), 0, ctx->stream,
+		                   (Cand *)ctx->block_out, total, k, total,
+		                   (Cand *)ctx->final_out);
+	}
+}
+
 // Launch the all-distances computation for any metric (q already staged in
 // ctx->q_dev). Jaccard runs its block-per-row LDS-set kernel; the rest run
 // the per-lane k_all_dists chain.
@@ -3708,16 +3522,19 @@ static void launch_all_dists(sdbv_ctx *ctx, Table &t, const float *q,
 // scan kernel's LDS top-K window (MAX_K), and the product path proper for
 // the six non-headline metrics (SURVEY §8 a2 closure). ids are strictly
 // increasing, so (dist, row) order equals the contract's (dist, id)
-// order. Costs one n-f64 D2H per query. Caller holds ctx->mu.
+// order. Costs one n-f64 D2H per query. Under a filter (allow not null:
+// ceil(n / 64) validated words) the host selection skips the rows the bitmap
+// does not allow, and last_rows_scanned is the caller's. Caller holds
+// ctx->mu.
 static int knn_large_k(sdbv_ctx *ctx, Table &t, const float *q, uint32_t d,
-                       uint32_t k, uint64_t *out_ids, double *out_dists,
-                       uint32_t *out_n) {
+                       uint32_t k, const uint64_t *allow, uint64_t *out_ids,
+                       double *out_dists, uint32_t *out_n) {
 	int rc = ensure_query_scratch(ctx, d, 1, 1);
 	if (rc != SDBV_OK)
 		return rc;
-	std::memcpy(ctx->q_pin, q, d * sizeof(float)); // pinned staging
-	HIP_CHECK(ctx, hipMemcpyAsync(ctx->q_dev, ctx->q_pin, d * sizeof(float),
-	                              hipMemcpyHostToDevice, ctx->stream));
+	rc = stage_query(ctx, q, d, d * sizeof(float));
+	if (rc != SDBV_OK)
+		return rc;
 	double *dout = nullptr;
 	HIP_CHECK(ctx, hipMalloc(&dout, t.n * sizeof(double)));
 	HIP_CHECK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
@@ -3740,7 +3557,8 @@ static int knn_large_k(sdbv_ctx *ctx, Table &t, const float *q, uint32_t d,
 	(void)hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1);
 	ctx->stats.last_scan_kernel_ms = ms;
 	ctx->stats.last_merge_kernel_ms = 0;
-	ctx->stats.last_rows_scanned = t.n;
+	if (!allow)
+		ctx->stats.last_rows_scanned = t.n;
 	// bounded max-heap of (total_key(dist), row): keep the k smallest
 	auto tkey = [](double x) {
 		uint64_t bits;
@@ -3749,6 +3567,8 @@ static int knn_large_k(sdbv_ctx *ctx, Table &t, const float *q, uint32_t d,
 	};
 	std::priority_queue<std::pair<uint64_t, uint64_t>> heap;
 	for (uint64_t r = 0; r < t.n; r++) {
+		if (allow && !((allow[r >> 6] >> (r & 63)) & 1ULL))
+			continue;
 		std::pair<uint64_t, uint64_t> e{tkey(hd[r]), r};
 		if (heap.size() < k) {
 			heap.push(e);
@@ -3768,25 +3588,25 @@ static int knn_large_k(sdbv_ctx *ctx, Table &t, const float *q, uint32_t d,
 	return SDBV_OK;
 }
 
-// Row-span grid of the prefilter sweep: contiguous spans of PF_TILE-row
-// tiles, sized so that the whole grid is resident at once (one round, every
-// block the same span). A grid of a few more blocks than the chip holds runs
-// a second, mostly empty round with too few bytes in flight per CU — 3.5 %
-// of the kernel at 10M rows (profiles/prefilter_scan.md).
+// Row-span grid of the prefilter sweep of shadow tier kind (1..3): contiguous
+// spans of the tier's tiles, sized so that the whole grid is resident at once
+// (one round, every block the same span). A grid of a few more blocks than
+// the chip holds runs a second, mostly empty round with too few bytes in
+// flight per CU — 3.5 % of the kernel at 10M rows
+// (profiles/prefilter_scan.md).
 static uint64_t prefilter_grid(sdbv_ctx *ctx, uint64_t n, int kind,
                                uint64_t *rows_per_block) {
-	uint64_t &slots = kind == 3   ? ctx->pf6_slots
-	                  : kind == 2 ? ctx->pf8_slots
-	                              : ctx->pf_slots;
+	uint64_t &slots = ctx->pf_slots[kind];
 	if (slots == 0) {
 		int per_cu = 0, cus = 0;
-		hipError_t e =
-		    kind == 3   ? hipOccupancyMaxActiveBlocksPerMultiprocessor(
-		                      &per_cu, k_prefilter_i6, THREADS, 0)
-		    : kind == 2 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(
-		                      &per_cu, k_prefilter_i8, THREADS, 0)
-		                : hipOccupancyMaxActiveBlocksPerMultiprocessor(
-		                      &per_cu, k_prefilter, THREADS, 0);
+		const void *kernel = nullptr;
+		switch (kind) {
+		case 1: kernel = (const void *)k_prefilter; break;
+		case 2: kernel = (const void *)k_prefilter_i8; break;
+		case 3: kernel = (const void *)k_prefilter_i6; break;
+		}
+		hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(
+		    &per_cu, kernel, THREADS, 0);
 		if (e != hipSuccess ||
 		    hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount,
 		                          ctx->device) != hipSuccess ||
@@ -3797,7 +3617,7 @@ static uint64_t prefilter_grid(sdbv_ctx *ctx, uint64_t n, int kind,
 			slots = (uint64_t)per_cu * (uint64_t)cus;
 		}
 	}
-	const uint64_t tile = kind == 3 ? PF6_TILE : kind == 2 ? PF8_TILE : PF_TILE;
+	const uint64_t tile = SHADOW_TIERS[kind].tile;
 	uint64_t tiles = (n + tile - 1) / tile;
 	uint64_t nblocks = tiles < slots ? tiles : slots;
 	if (nblocks == 0)
@@ -3807,34 +3627,32 @@ static uint64_t prefilter_grid(sdbv_ctx *ctx, uint64_t n, int kind,
 	return (n + *rows_per_block - 1) / *rows_per_block;
 }
 
-// The prefilter path of sdbv_knn_bruteforce (cosine, k <= MAX_K, table with
-// a shadow, query inside the norm window; q already in ctx->q_dev and the
-// query scratch sized for prefilter_grid). host_out[0..k) receives the
-// exact top-k, *ncand the candidate count; *ncand > PF_CAND_CAP means the
-// list overflowed and host_out is void: the caller runs the exact scan.
-// One D2H copy and one sync, like the exact path. Caller holds ctx->mu.
 struct PfQ6 { // int6 tier: the quantised query's kernel operands
 	float qscale = 0.f; // f32(sq / |q|)
 	float qeps = 0.f;   // 1.01 rho_q, rounded up
 	uint32_t bias = 0;  // 65536 d_pad - 32 sum qu (mod 2^32)
 };
 
-static inline int shadow_kind(const Table &t) {
-	return t.shadow6 ? 3 : t.shadow8 ? 2 : t.shadow ? 1 : 0;
-}
+static inline int shadow_kind(const Table &t) { return t.sh.kind; }
 
+// The prefilter path of sdbv_knn_bruteforce (cosine, k <= MAX_K, table with
+// a shadow, query inside the norm window; q already in ctx->q_dev and the
+// query scratch sized for prefilter_grid). host_out[0..k) receives the
+// exact top-k, *ncand the candidate count; *ncand > PF_CAND_CAP means the
+// list overflowed and host_out is void: the caller runs the exact scan.
+// One D2H copy and one sync, like the exact path. Caller holds ctx->mu.
 static int knn_prefilter(sdbv_ctx *ctx, Table &t, uint32_t k, double q_norm,
                          float qbias, const PfQ6 &q6, Cand *host_out,
                          uint32_t *ncand) {
-	const int kind = shadow_kind(t);
-	const bool i8 = kind >= 2; // per-row bounds: zero compact window
-	if (ctx->pf_scores_cap < t.sn_pad) {
+	const Shadow &sh = t.sh;
+	const int kind = sh.kind;
+	if (ctx->pf_scores_cap < sh.sn_pad) {
 		if (ctx->pf_scores)
 			(void)hipFree(ctx->pf_scores);
 		ctx->pf_scores = nullptr;
 		ctx->pf_scores_cap = 0;
-		HIP_CHECK(ctx, hipMalloc(&ctx->pf_scores, t.sn_pad * sizeof(float)));
-		ctx->pf_scores_cap = t.sn_pad;
+		HIP_CHECK(ctx, hipMalloc(&ctx->pf_scores, sh.sn_pad * sizeof(float)));
+		ctx->pf_scores_cap = sh.sn_pad;
 	}
 	if (!ctx->pf_rows)
 		HIP_CHECK(ctx, hipMalloc(&ctx->pf_rows,
@@ -3853,45 +3671,37 @@ static int knn_prefilter(sdbv_ctx *ctx, Table &t, uint32_t k, double q_norm,
 	const float inv_q = (float)(1.0 / q_norm);
 
 	HIP_CHECK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-	if (kind == 3)
+	switch (kind) {
+	case 1:
+		hipLaunchKernelGGL(k_prefilter, dim3((uint32_t)nblocks), dim3(THREADS),
+		                   0, ctx->stream, (const uint16_t *)sh.codes,
+		                   sh.pinv(), t.n, sh.sn_pad, t.d, ctx->q_dev, inv_q, k,
+		                   rows_per_block, ctx->pf_scores,
+		                   (Cand *)ctx->block_out, cand_cnt);
+		break;
+	case 2:
+		hipLaunchKernelGGL(k_prefilter_i8, dim3((uint32_t)nblocks),
+		                   dim3(THREADS), 0, ctx->stream,
+		                   (const uint8_t *)sh.codes, sh.pscale(), sh.peps(),
+		                   t.n, sh.sn_pad, t.d, ctx->q_dev, inv_q, qbias, k,
+		                   rows_per_block, ctx->pf_scores,
+		                   (Cand *)ctx->block_out, cand_cnt);
+		break;
+	case 3:
 		hipLaunchKernelGGL(k_prefilter_i6, dim3((uint32_t)nblocks),
 		                   dim3(THREADS), 0, ctx->stream,
-		                   (const uint4 *)t.shadow6, (const uint2 *)t.shadow6l,
-		                   t.pscale, t.peps, t.xsum, t.n, t.sn_pad,
+		                   (const uint4 *)sh.plane_h(),
+		                   (const uint2 *)sh.plane_l(t.d), sh.pscale(),
+		                   sh.peps(), sh.xsum(), t.n, sh.sn_pad,
 		                   (t.d + 31) / 32, (const uint32_t *)(ctx->q_dev + t.d),
 		                   q6.qscale, q6.qeps, q6.bias, k, rows_per_block,
 		                   ctx->pf_scores, (Cand *)ctx->block_out, cand_cnt);
-	else if (kind == 2)
-		hipLaunchKernelGGL(k_prefilter_i8, dim3((uint32_t)nblocks),
-		                   dim3(THREADS), 0, ctx->stream, t.shadow8, t.pscale,
-		                   t.peps, t.n, t.sn_pad, t.d, ctx->q_dev, inv_q, qbias,
-		                   k, rows_per_block, ctx->pf_scores,
-		                   (Cand *)ctx->block_out, cand_cnt);
-	else
-		hipLaunchKernelGGL(k_prefilter, dim3((uint32_t)nblocks), dim3(THREADS),
-		                   0, ctx->stream, t.shadow, t.pinv, t.n, t.sn_pad,
-		                   t.d, ctx->q_dev, inv_q, k, rows_per_block,
-		                   ctx->pf_scores, (Cand *)ctx->block_out, cand_cnt);
-	HIP_CHECK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
-	{
-		// K smallest approximate distances (int8: upper bounds) ->
-		// final_out (A_K, or U_K, = entry k-1)
-		uint64_t total = nblocks * k;
-		const uint64_t G = 32;
-		if (total > 4096 && nblocks > G) {
-			uint64_t per = ((nblocks + G - 1) / G) * k;
-			hipLaunchKernelGGL(k_merge, dim3((uint32_t)G), dim3(THREADS),
-			                   0, ctx->stream, (Cand *)ctx->block_out,
-			                   total, k, per, (Cand *)ctx->merge_tmp);
-			hipLaunchKernelGGL(k_merge, dim3(1), dim3(THREADS), 0,
-			                   ctx->stream, (Cand *)ctx->merge_tmp, G * k,
-			                   k, G * k, (Cand *)ctx->final_out);
-		} else {
-			hipLaunchKernelGGL(k_merge, dim3(1), dim3(THREADS), 0,
-			                   ctx->stream, (Cand *)ctx->block_out, total,
-			                   k, total, (Cand *)ctx->final_out);
-		}
+		break;
 	}
+	HIP_CHECK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+	// K smallest approximate distances (int8, int6: upper bounds) ->
+	// final_out (A_K, or U_K, = entry k-1)
+	launch_merge_tree(ctx, nblocks, k);
 	HIP_CHECK(ctx, hipEventRecord(ctx->ev2, ctx->stream));
 	{
 		uint64_t ngrp = (t.n + 3) / 4;
@@ -3903,7 +3713,9 @@ static int knn_prefilter(sdbv_ctx *ctx, Table &t, uint32_t k, double q_norm,
 		hipLaunchKernelGGL(k_pf_compact, dim3((uint32_t)nb), dim3(THREADS), 0,
 		                   ctx->stream, ctx->pf_scores, t.n,
 		                   (const Cand *)ctx->final_out, k,
-		                   i8 ? 0.0f : pf_eps(t.d), cand_cnt, ctx->pf_rows);
+		                   // per-row bounds (int8, int6): no window on top
+		                   kind == 1 ? pf_eps(t.d) : 0.0f, cand_cnt,
+		                   ctx->pf_rows);
 		hipLaunchKernelGGL(k_pf_rescore, dim3(PF_RESCORE_BLOCKS), dim3(64), 0,
 		                   ctx->stream, t.cm, t.norms, t.ids_dev, t.n_pad,
 		                   t.d, ctx->q_dev, q_norm, cand_cnt, ctx->pf_rows,
@@ -3937,36 +3749,9 @@ static int knn_exact_scan(sdbv_ctx *ctx, Table &t, uint32_t k, double q_norm,
                           uint64_t nblocks, uint64_t rows_per_block,
                           Cand *host_out) {
 	HIP_CHECK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-	if (t.metric == SDBV_METRIC_COSINE)
-		hipLaunchKernelGGL(k_scan<0>, dim3((uint32_t)nblocks), dim3(THREADS), 0,
-		                   ctx->stream, t.cm, t.norms, t.n, t.n_pad, t.d,
-		                   ctx->q_dev, q_norm, k, rows_per_block,
-		                   (Cand *)ctx->block_out, t.ids_dev);
-	else
-		hipLaunchKernelGGL(k_scan<1>, dim3((uint32_t)nblocks), dim3(THREADS), 0,
-		                   ctx->stream, t.cm, t.norms, t.n, t.n_pad, t.d,
-		                   ctx->q_dev, q_norm, k, rows_per_block,
-		                   (Cand *)ctx->block_out, t.ids_dev);
+	launch_scan(ctx, t, k, q_norm, nblocks, rows_per_block, nullptr);
 	HIP_CHECK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
-	{
-		uint64_t total = nblocks * k;
-		const uint64_t G = 32; // level-1 fan-in
-		if (total > 4096 && nblocks > G) {
-			// two-level tree merge: G slices in parallel, then one block
-			// over G*k (scratch lives past final_out's k entries)
-			uint64_t per = ((nblocks + G - 1) / G) * k;
-			hipLaunchKernelGGL(k_merge, dim3((uint32_t)G), dim3(THREADS),
-			                   0, ctx->stream, (Cand *)ctx->block_out,
-			                   total, k, per, (Cand *)ctx->merge_tmp);
-			hipLaunchKernelGGL(k_merge, dim3(1), dim3(THREADS), 0,
-			                   ctx->stream, (Cand *)ctx->merge_tmp, G * k,
-			                   k, G * k, (Cand *)ctx->final_out);
-		} else {
-			hipLaunchKernelGGL(k_merge, dim3(1), dim3(THREADS), 0,
-			                   ctx->stream, (Cand *)ctx->block_out, total,
-			                   k, total, (Cand *)ctx->final_out);
-		}
-	}
+	launch_merge_tree(ctx, nblocks, k);
 	HIP_CHECK(ctx, hipEventRecord(ctx->ev2, ctx->stream));
 	HIP_CHECK(ctx, hipMemcpyAsync(host_out, ctx->final_out, k * sizeof(Cand),
 	                              hipMemcpyDeviceToHost, ctx->stream));
@@ -3997,21 +3782,16 @@ int sdbv_knn_bruteforce(sdbv_ctx *ctx, uint64_t table, const float *q,
 	ctx->stats.last_scan_path = 0;
 	ctx->stats.last_prefilter_candidates = 0;
 	if (k > MAX_K || t.metric > SDBV_METRIC_EUCLIDEAN)
-		return knn_large_k(ctx, t, q, d, k, out_ids, out_dists, out_n);
+		return knn_large_k(ctx, t, q, d, k, nullptr, out_ids, out_dists,
+		                   out_n);
 
-	// pick a grid: >=2048 blocks to fill 256 CUs, contiguous spans per block
-	uint64_t tiles = (t.n + TILE - 1) / TILE;
-	uint64_t nblocks = tiles < 2048 ? tiles : 2048;
-	if (nblocks == 0)
-		nblocks = 1;
-	uint64_t tiles_per_block = (tiles + nblocks - 1) / nblocks;
-	uint64_t rows_per_block = tiles_per_block * TILE;
-	nblocks = (t.n + rows_per_block - 1) / rows_per_block;
-
+	uint64_t rows_per_block = 0;
+	const uint64_t nblocks = scan_grid(t.n, &rows_per_block);
+	// block_out serves whichever of the two grids runs
+	const int kind = shadow_kind(t);
 	uint64_t pf_rows_per_block = 0;
 	uint64_t scratch_blocks = std::max(
-	    nblocks,
-	    prefilter_grid(ctx, t.n, shadow_kind(t), &pf_rows_per_block));
+	    nblocks, kind ? prefilter_grid(ctx, t.n, kind, &pf_rows_per_block) : 0);
 	int rc = ensure_query_scratch(ctx, d, scratch_blocks, k);
 	if (rc != SDBV_OK)
 		return rc;
@@ -4020,10 +3800,8 @@ int sdbv_knn_bruteforce(sdbv_ctx *ctx, uint64_t table, const float *q,
 	// the window the bound is proven for (a non-finite element makes the
 	// norm non-finite). Everything else, and a query whose candidate list
 	// overflowed, takes the exact scan; results never depend on the choice.
-	const int kind = shadow_kind(t);
 	const bool use_pf =
 	    kind != 0 && q_norm >= PF_NORM_MIN && q_norm <= PF_NORM_MAX;
-	std::memcpy(ctx->q_pin, q, d * sizeof(float)); // pinned staging
 	size_t q_bytes = d * sizeof(float);
 	PfQ6 q6;
 	if (use_pf && kind == 3) {
@@ -4038,15 +3816,16 @@ int sdbv_knn_bruteforce(sdbv_ctx *ctx, uint64_t table, const float *q,
 		q6.qeps = rho > 0.f ? pf_round_up_f32(1.01 * (double)rho) : 0.f;
 		q6.bias = 65536u * (32u * G) - 32u * qs;
 	}
-	HIP_CHECK(ctx, hipMemcpyAsync(ctx->q_dev, ctx->q_pin, q_bytes,
-	                              hipMemcpyHostToDevice, ctx->stream));
+	rc = stage_query(ctx, q, d, q_bytes);
+	if (rc != SDBV_OK)
+		return rc;
 
 	auto t_start = std::chrono::steady_clock::now();
 	Cand host_out[MAX_K + 1];
 	if (use_pf) {
 		// int8 tier: the bias term 128 * sum q_k, one f64 sum rounded once
 		double qsum = 0.0;
-		if (t.shadow8)
+		if (kind == 2)
 			for (uint32_t i = 0; i < d; i++)
 				qsum += (double)q[i];
 		uint32_t ncand = 0;
@@ -4069,12 +3848,8 @@ int sdbv_knn_bruteforce(sdbv_ctx *ctx, uint64_t table, const float *q,
 	        std::chrono::steady_clock::now() - t_start)
 	        .count();
 
-	uint32_t m = (uint32_t)(k < t.n ? k : t.n);
-	*out_n = m;
-	for (uint32_t i = 0; i < m; i++) {
-		out_ids[i] = host_out[i].id;
-		out_dists[i] = host_out[i].dist;
-	}
+	copy_results(host_out, (uint32_t)(k < t.n ? k : t.n), out_ids, out_dists,
+	             out_n);
 	return SDBV_OK;
 }
 
@@ -4128,91 +3903,8 @@ static uint64_t filter_rowlist_max() {
 	return cap;
 }
 
-// knn_large_k under a filter: the same all-distances launch, and a host
-// selection that skips the rows the bitmap does not allow. Caller holds
-// ctx->mu and has validated allow (ceil(n / 64) words).
-static int knn_large_k_filtered(sdbv_ctx *ctx, Table &t, const float *q,
-                                uint32_t d, uint32_t k, const uint64_t *allow,
-                                uint64_t *out_ids, double *out_dists,
-                                uint32_t *out_n) {
-	int rc = ensure_query_scratch(ctx, d, 1, 1);
-	if (rc != SDBV_OK)
-		return rc;
-	std::memcpy(ctx->q_pin, q, d * sizeof(float)); // pinned staging
-	HIP_CHECK(ctx, hipMemcpyAsync(ctx->q_dev, ctx->q_pin, d * sizeof(float),
-	                              hipMemcpyHostToDevice, ctx->stream));
-	double *dout = nullptr;
-	HIP_CHECK(ctx, hipMalloc(&dout, t.n * sizeof(double)));
-	HIP_CHECK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-	launch_all_dists(ctx, t, q, dout);
-	HIP_CHECK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
-	std::vector<double> hd(t.n);
-	std::vector<uint64_t> hids(t.n);
-	if (hipMemcpyAsync(hd.data(), dout, t.n * sizeof(double),
-	                   hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-	    hipMemcpyAsync(hids.data(), t.ids_dev, t.n * sizeof(uint64_t),
-	                   hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-	    hipStreamSynchronize(ctx->stream) != hipSuccess ||
-	    hipGetLastError() != hipSuccess) {
-		(void)hipFree(dout);
-		ctx->err = "knn_large_k_filtered: device error";
-		return SDBV_ERR_HIP;
-	}
-	(void)hipFree(dout);
-	float ms = 0;
-	(void)hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1);
-	ctx->stats.last_scan_kernel_ms = ms;
-	ctx->stats.last_merge_kernel_ms = 0;
-	// bounded max-heap of (total_key(dist), row) over the allowed rows
-	auto tkey = [](double x) {
-		uint64_t bits;
-		std::memcpy(&bits, &x, 8);
-		return (bits >> 63) ? ~bits : (bits | 0x8000000000000000ULL);
-	};
-	std::priority_queue<std::pair<uint64_t, uint64_t>> heap;
-	for (uint64_t r = 0; r < t.n; r++) {
-		if (!((allow[r >> 6] >> (r & 63)) & 1ULL))
-			continue;
-		std::pair<uint64_t, uint64_t> e{tkey(hd[r]), r};
-		if (heap.size() < k) {
-			heap.push(e);
-		} else if (e < heap.top()) {
-			heap.pop();
-			heap.push(e);
-		}
-	}
-	uint32_t m = (uint32_t)heap.size();
-	*out_n = m;
-	for (uint32_t i = m; i-- > 0;) {
-		auto e = heap.top();
-		heap.pop();
-		out_ids[i] = hids[e.second];
-		out_dists[i] = hd[e.second];
-	}
-	return SDBV_OK;
-}
-
-// The k_merge tree over nblocks * k block winners, as knn_exact_scan runs it.
-static void launch_merge_tree(sdbv_ctx *ctx, uint64_t nblocks, uint32_t k) {
-	uint64_t total = nblocks * k;
-	const uint64_t G = 32; // level-1 fan-in
-	if (total > 4096 && nblocks > G) {
-		uint64_t per = ((nblocks + G - 1) / G) * k;
-		hipLaunchKernelGGL(k_merge, dim3((uint32_t)G), dim3(THREADS), 0,
-		                   ctx->stream, (Cand *)ctx->block_out, total, k, per,
-		                   (Cand *)ctx->merge_tmp);
-		hipLaunchKernelGGL(k_merge, dim3(1), dim3(THREADS), 0, ctx->stream,
-		                   (Cand *)ctx->merge_tmp, G * k, k, G * k,
-		                   (Cand *)ctx->final_out);
-	} else {
-		hipLaunchKernelGGL(k_merge, dim3(1), dim3(THREADS), 0, ctx->stream,
-		                   (Cand *)ctx->block_out, total, k, total,
-		                   (Cand *)ctx->final_out);
-	}
-}
-
 // Masked scan of the filtered call: upload the bitmap (tail cleared,
-// zero-filled to n_pad / 64 words), k_scan_masked over k_scan's grid, the
+// zero-filled to n_pad / 64 words), k_scan<., true> over scan_grid, the
 // merge tree. q already in ctx->q_dev, scratch sized for nblocks. Caller
 // holds ctx->mu.
 static int knn_masked_scan(sdbv_ctx *ctx, Table &t, uint32_t k, double q_norm,
@@ -4242,16 +3934,7 @@ static int knn_masked_scan(sdbv_ctx *ctx, Table &t, uint32_t k, double q_norm,
 	                              mwords * sizeof(uint64_t),
 	                              hipMemcpyHostToDevice, ctx->stream));
 	HIP_CHECK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-	if (t.metric == SDBV_METRIC_COSINE)
-		hipLaunchKernelGGL(k_scan_masked<0>, dim3((uint32_t)nblocks),
-		                   dim3(THREADS), 0, ctx->stream, t.cm, t.norms, t.n,
-		                   t.n_pad, t.d, ctx->q_dev, q_norm, k, rows_per_block,
-		                   (Cand *)ctx->block_out, t.ids_dev, ctx->flt_mask);
-	else
-		hipLaunchKernelGGL(k_scan_masked<1>, dim3((uint32_t)nblocks),
-		                   dim3(THREADS), 0, ctx->stream, t.cm, t.norms, t.n,
-		                   t.n_pad, t.d, ctx->q_dev, q_norm, k, rows_per_block,
-		                   (Cand *)ctx->block_out, t.ids_dev, ctx->flt_mask);
+	launch_scan(ctx, t, k, q_norm, nblocks, rows_per_block, ctx->flt_mask);
 	HIP_CHECK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
 	launch_merge_tree(ctx, nblocks, k);
 	HIP_CHECK(ctx, hipEventRecord(ctx->ev2, ctx->stream));
@@ -4334,23 +4017,19 @@ int sdbv_knn_bruteforce_filtered(sdbv_ctx *ctx, uint64_t table, const float *q,
 		return SDBV_OK;
 	}
 	if (!device_topk)
-		return knn_large_k_filtered(ctx, t, q, d, k, allow, out_ids, out_dists,
-		                            out_n);
+		return knn_large_k(ctx, t, q, d, k, allow, out_ids, out_dists, out_n);
 
 	const bool by_list = count <= list_max;
 	// the masked scan runs on k_scan's grid
-	uint64_t tiles = (t.n + TILE - 1) / TILE;
-	uint64_t nblocks = tiles < 2048 ? tiles : 2048;
-	uint64_t tiles_per_block = (tiles + nblocks - 1) / nblocks;
-	uint64_t rows_per_block = tiles_per_block * TILE;
-	nblocks = (t.n + rows_per_block - 1) / rows_per_block;
+	uint64_t rows_per_block = 0;
+	const uint64_t nblocks = scan_grid(t.n, &rows_per_block);
 	int rc = ensure_query_scratch(ctx, d, by_list ? 1 : nblocks, k);
 	if (rc != SDBV_OK)
 		return rc;
 	double q_norm = sqrt((double)h_sumsq_f32(q, d));
-	std::memcpy(ctx->q_pin, q, d * sizeof(float)); // pinned staging
-	HIP_CHECK(ctx, hipMemcpyAsync(ctx->q_dev, ctx->q_pin, d * sizeof(float),
-	                              hipMemcpyHostToDevice, ctx->stream));
+	rc = stage_query(ctx, q, d, d * sizeof(float));
+	if (rc != SDBV_OK)
+		return rc;
 	Cand host_out[MAX_K];
 	if (by_list)
 		rc = knn_row_list(ctx, t, k, q_norm, (uint32_t)count, host_out);
@@ -4370,12 +4049,8 @@ int sdbv_knn_bruteforce_filtered(sdbv_ctx *ctx, uint64_t table, const float *q,
 	        std::chrono::steady_clock::now() - t_start)
 	        .count();
 
-	uint32_t m = (uint32_t)(k < count ? k : count);
-	*out_n = m;
-	for (uint32_t i = 0; i < m; i++) {
-		out_ids[i] = host_out[i].id;
-		out_dists[i] = host_out[i].dist;
-	}
+	copy_results(host_out, (uint32_t)(k < count ? k : count), out_ids,
+	             out_dists, out_n);
 	return SDBV_OK;
 }
 
@@ -4473,7 +4148,7 @@ int sdbv_knn_batch(sdbv_ctx *ctx, uint64_t table, const float *Q, uint32_t b,
 		// batch path is only for the genuinely dense cosine/euclidean case)
 		for (uint32_t j = 0; j < b; j++) {
 			uint32_t m = 0;
-			int rc = knn_large_k(ctx, t, Q + (uint64_t)j * d, d, k,
+			int rc = knn_large_k(ctx, t, Q + (uint64_t)j * d, d, k, nullptr,
 			                     out_ids + (uint64_t)j * k,
 			                     out_dists + (uint64_t)j * k, &m);
 			if (rc)
