@@ -96,7 +96,10 @@ typedef struct sdbv_stats {
 	                            prefilter overflowed, then exact scan, 5 = int6
 	                            prefilter, 6 = int6 prefilter overflowed, then
 	                            exact scan. sdbv_knn_bruteforce_filtered: 7 =
-	                            masked scan, 8 = row-list path, 0 = the
+	                            masked scan, 8 = row-list path, 9 = bf16
+	                            prefilter under the bitmap, 10 = that
+	                            overflowed, then masked scan, 11 / 12 = the
+	                            same for int8, 13 / 14 for int6, 0 = the
 	                            all-distances route */
 	uint64_t last_filter_rows; /* allowed rows of the last filtered call (for
 	                              such a call last_rows_scanned is the same
@@ -252,16 +255,26 @@ int sdbv_knn_bruteforce(sdbv_ctx *, uint64_t table, const float *q, uint32_t d,
  * Result contract: that of sdbv_knn_bruteforce over the allowed rows only —
  * ascending (distance f64 total_cmp, id), distance bits of the exact chain,
  * *out_n = min(k, allowed rows); no allowed row gives *out_n = 0, SDBV_OK and
- * no launch. The exact f32 store serves every filtered call; a prefilter
- * shadow is neither used nor disturbed.
+ * no launch. The path never changes a result.
  * COSINE/EUCLIDEAN with k <= 64 run on-device: at most
  * SDBV_FILTER_ROWLIST_MAX allowed rows (environment, read at each call,
  * default and ceiling 16384; 0 = never) are listed by the host and gathered
- * one workgroup per row (last_scan_path 8); more run the masked scan, k_scan
- * with the bitmap as a second validity test, which skips every 256-row
- * segment without an allowed row (last_scan_path 7). Other metrics and larger
- * k take the all-distances launch with a host selection that skips the rows
- * not allowed (last_scan_path 0). */
+ * one workgroup per row (last_scan_path 8). More allowed rows than that
+ * stream the table's prefilter shadow under the bitmap when the table is
+ * cosine and has a shadow of any kind, the query norm lies in
+ * [2^-30, 2^30], SDBV_FILTER_PREFILTER is not 0 and the table has at least
+ * SDBV_FILTER_PREFILTER_MIN_ROWS rows (both environment, read at each call;
+ * default 500000): the tier's prefilter with its threshold taken over the
+ * allowed rows and only allowed rows as candidates, then the exact rescore
+ * (last_scan_path 9 bf16, 11 int8, 13 int6). A wave skips the rows of its
+ * span when none of them is allowed: 512 rows (bf16), 1024 (int8), 64
+ * (int6). More than 16384 candidates rerun the call as the masked scan
+ * (10, 12, 14). Every other call runs the masked scan, k_scan with the
+ * bitmap as a second validity test, which skips every 256-row segment
+ * without an allowed row (last_scan_path 7). The shadow is only read: an
+ * unfiltered call before or after is not disturbed. Other metrics and
+ * larger k take the all-distances launch with a host selection that skips
+ * the rows not allowed (last_scan_path 0). */
 int sdbv_knn_bruteforce_filtered(sdbv_ctx *, uint64_t table, const float *q,
                                  uint32_t d, uint32_t k,
                                  const uint64_t *allow, uint64_t allow_words,

@@ -294,7 +294,16 @@ class Context:
     def knn_bruteforce_filtered(self, table, q, k, allow):
         """knn_bruteforce over the allowed rows only. `allow` is a bool
         array with one entry per staged row, or the ready uint64 bitmap
-        (row r = bit r & 63 of word r >> 6). Returns (ids, dists)."""
+        (row r = bit r & 63 of word r >> 6). Returns (ids, dists).
+
+        The path is the library's choice and never changes the result: the
+        row list for at most SDBV_FILTER_ROWLIST_MAX (16384) allowed rows
+        (stats last_scan_path 8); the table's prefilter shadow streamed under
+        the bitmap on a shadowed cosine table of at least
+        SDBV_FILTER_PREFILTER_MIN_ROWS (500000) rows, k <= 64, unless
+        SDBV_FILTER_PREFILTER=0 (9 / 11 / 13 by tier, the even number after
+        it when the candidate list overflowed); the masked exact scan
+        otherwise (7)."""
         import numpy as np
         q = np.ascontiguousarray(q, dtype=np.float32)
         n = self.table_rows(table)

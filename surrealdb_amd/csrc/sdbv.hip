@@ -143,8 +143,8 @@ struct sdbv_ctx {
 	uint32_t *pf_rows = nullptr; // [PF_CAND_CAP] candidate rows
 	void *pf_cands = nullptr;    // [PF_CAND_CAP] rescored Cand
 	void *pf_res = nullptr;      // [MAX_K + 2] Cand: top-k, the count, counter
-	uint64_t pf_slots[4] = {};   // by Shadow::kind: blocks of that tier's
-	                             // prefilter kernel the device holds at once
+	uint64_t pf_slots[2][4] = {}; // by MASKED and Shadow::kind: blocks of that
+	                              // prefilter kernel the device holds at once
 	// batched path
 	rocblas_handle blas = nullptr;
 	float *S = nullptr; // chunk scores scratch, [chunk][b] col-major
@@ -166,8 +166,9 @@ struct sdbv_ctx {
 	uint64_t bcand_cnt_cap = 0;
 	double ms_gemm = 0, ms_select = 0, ms_exact = 0; // last batch timings
 	// filtered brute-force scratch (sdbv_knn_bruteforce_filtered), its own:
-	// nothing here is shared with the prefilter tiers
-	uint64_t *flt_mask = nullptr;     // [n_pad / 64] allowed-row bitmap, device
+	// the unfiltered call touches nothing here
+	uint64_t *flt_mask = nullptr;     // [max(n_pad, sn_pad) / 64] allowed-row
+	                                  // bitmap, device
 	uint64_t *flt_mask_pin = nullptr; // pinned copy with the tail bits cleared
 	uint64_t flt_mask_cap = 0;        // words, both buffers
 	uint32_t *flt_rows = nullptr;     // [PF_CAND_CAP] allowed rows, device
@@ -868,12 +869,25 @@ __device__ __forceinline__ static void pf_topk_write(
 // scores are stored as -inf, so k_pf_compact always passes them on, and are
 // kept OUT of the top-K: the threshold must come from K rows that do carry
 // the bound. Block 0 also clears the candidate counter for k_pf_compact.
+//
+// MASKED (the filtered call), in all three prefilter kernels:
+// mask holds sn_pad / 64 words, no bit set at or past n. A row whose bit is
+// clear is invalid for the block top-K like a row past row_end, and its
+// score is stored as NaN, which k_pf_compact never passes, not even against
+// a threshold of +inf; -inf stays what it is, an ALLOWED row the bound does
+// not cover. Every row below n is written by every call, so no score of an
+// earlier call survives. A wave none of whose rows is allowed skips the
+// loads and the accumulation: a wave-uniform branch (a ballot) around the
+// feature loop alone, never around a barrier or the scores[] store. Here a
+// lane's 8 rows are one byte of one mask word, a wave's 512 rows 8 words.
+// Without MASKED, mask is never read (nullptr).
+template <bool MASKED>
 __global__ __launch_bounds__(THREADS) void k_prefilter(
     const uint16_t *__restrict__ sh, const float *__restrict__ pinv,
     uint64_t n, uint64_t sn_pad, uint32_t d, const float *__restrict__ qg,
     float inv_qnorm, uint32_t k, uint64_t rows_per_block,
     float *__restrict__ scores, Cand *__restrict__ block_out,
-    uint32_t *__restrict__ cand_cnt) {
+    uint32_t *__restrict__ cand_cnt, const uint64_t *__restrict__ mask) {
 	__shared__ uint64_t buf[PF_TILE + MAX_K];
 	__shared__ uint64_t topk[MAX_K];
 	__shared__ int cnt;
@@ -887,6 +901,7 @@ __global__ __launch_bounds__(THREADS) void k_prefilter(
 	if (row_end > n)
 		row_end = n;
 	const float ninf = __uint_as_float(0xFF800000u);
+	const float qnan = __uint_as_float(0x7FC00000u);
 
 	for (uint64_t tile_base = row_begin; tile_base < row_end;
 	     tile_base += PF_TILE) {
@@ -894,6 +909,13 @@ __global__ __launch_bounds__(THREADS) void k_prefilter(
 		    tile_base + (uint64_t)threadIdx.x * PF_ROWS_PER_LANE;
 		const uint16_t *p = sh + r0;
 		float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+		uint32_t mb = 0xFFu; // the lane's 8 mask bits
+		bool live = true;
+		if constexpr (MASKED) {
+			// r0 + 8 <= tile_base + PF_TILE <= sn_pad
+			mb = (uint32_t)(mask[r0 >> 6] >> (r0 & 63)) & 0xFFu;
+			live = __ballot(mb != 0u) != 0ULL;
+		}
 #define PF_ACC(V, qk)                                                          \
 	acc[0] = __fmaf_rn(__uint_as_float((V).x << 16), qk, acc[0]);              \
 	acc[1] = __fmaf_rn(__uint_as_float((V).x & 0xFFFF0000u), qk, acc[1]);      \
@@ -903,22 +925,24 @@ __global__ __launch_bounds__(THREADS) void k_prefilter(
 	acc[5] = __fmaf_rn(__uint_as_float((V).z & 0xFFFF0000u), qk, acc[5]);      \
 	acc[6] = __fmaf_rn(__uint_as_float((V).w << 16), qk, acc[6]);              \
 	acc[7] = __fmaf_rn(__uint_as_float((V).w & 0xFFFF0000u), qk, acc[7]);
-		uint32_t kk = 0;
-		for (; kk + 8 <= d; kk += 8) {
-			uint4 w[8];
+		if (live) {
+			uint32_t kk = 0;
+			for (; kk + 8 <= d; kk += 8) {
+				uint4 w[8];
 #pragma unroll
-			for (uint32_t j = 0; j < 8; j++)
-				w[j] = *(const uint4 *)(p + (uint64_t)(kk + j) * sn_pad);
+				for (uint32_t j = 0; j < 8; j++)
+					w[j] = *(const uint4 *)(p + (uint64_t)(kk + j) * sn_pad);
 #pragma unroll
-			for (uint32_t j = 0; j < 8; j++) {
-				const float qk = qg[kk + j]; // uniform: scalar load
-				PF_ACC(w[j], qk)
+				for (uint32_t j = 0; j < 8; j++) {
+					const float qk = qg[kk + j]; // uniform: scalar load
+					PF_ACC(w[j], qk)
+				}
 			}
-		}
-		for (; kk < d; kk++) {
-			const uint4 w1 = *(const uint4 *)(p + (uint64_t)kk * sn_pad);
-			const float qk = qg[kk];
-			PF_ACC(w1, qk)
+			for (; kk < d; kk++) {
+				const uint4 w1 = *(const uint4 *)(p + (uint64_t)kk * sn_pad);
+				const float qk = qg[kk];
+				PF_ACC(w1, qk)
+			}
 		}
 #undef PF_ACC
 		const float4 i0 = *(const float4 *)(pinv + r0);
@@ -932,6 +956,11 @@ __global__ __launch_bounds__(THREADS) void k_prefilter(
 			ok[c] = (r0 + c) < row_end &&
 			        (__float_as_uint(s) & 0x7F800000u) != 0x7F800000u;
 			a[c] = ok[c] ? s : ninf;
+			if constexpr (MASKED) {
+				const bool allowed = (mb >> c) & 1u;
+				ok[c] = ok[c] && allowed;
+				a[c] = allowed ? a[c] : qnan;
+			}
 		}
 		*(float4 *)(scores + r0) = make_float4(a[0], a[1], a[2], a[3]);
 		*(float4 *)(scores + r0 + 4) = make_float4(a[4], a[5], a[6], a[7]);
@@ -1079,13 +1108,16 @@ __global__ void k_shadow_i8(const float *__restrict__ cm,
 // u_i <= U_K have exact distances <= U_K, so the exact Kth distance D_K <=
 // U_K, and a true top-K row, ties included, has l_i <= d_i <= D_K <= U_K.
 // The 4096-row tile feeds the select in two 2048-row halves through the
-// same 17 KB buffer k_prefilter uses.
+// same 17 KB buffer k_prefilter uses. MASKED as in k_prefilter: a lane's 16
+// rows are 16 bits of one mask word, a wave's 1024 rows 16 words.
+template <bool MASKED>
 __global__ __launch_bounds__(THREADS) void k_prefilter_i8(
     const uint8_t *__restrict__ sh, const float *__restrict__ pscale,
     const float *__restrict__ peps, uint64_t n, uint64_t sn_pad, uint32_t d,
     const float *__restrict__ qg, float inv_qnorm, float qbias, uint32_t k,
     uint64_t rows_per_block, float *__restrict__ scores,
-    Cand *__restrict__ block_out, uint32_t *__restrict__ cand_cnt) {
+    Cand *__restrict__ block_out, uint32_t *__restrict__ cand_cnt,
+    const uint64_t *__restrict__ mask) {
 	__shared__ uint64_t buf[PF_TILE + MAX_K];
 	__shared__ uint64_t topk[MAX_K];
 	__shared__ int cnt;
@@ -1099,6 +1131,7 @@ __global__ __launch_bounds__(THREADS) void k_prefilter_i8(
 	if (row_end > n)
 		row_end = n;
 	const float ninf = __uint_as_float(0xFF800000u);
+	const float qnan = __uint_as_float(0x7FC00000u);
 
 	for (uint64_t tile_base = row_begin; tile_base < row_end;
 	     tile_base += PF8_TILE) {
@@ -1109,6 +1142,13 @@ __global__ __launch_bounds__(THREADS) void k_prefilter_i8(
 #pragma unroll
 		for (int c = 0; c < 16; c++)
 			acc[c] = 0.f;
+		uint32_t mb = 0xFFFFu; // the lane's 16 mask bits
+		bool live = true;
+		if constexpr (MASKED) {
+			// r0 + 16 <= tile_base + PF8_TILE <= sn_pad
+			mb = (uint32_t)(mask[r0 >> 6] >> (r0 & 63)) & 0xFFFFu;
+			live = __ballot(mb != 0u) != 0ULL;
+		}
 #define PF8_ACC4(W, qk, o)                                                     \
 	acc[o + 0] = __fmaf_rn((float)((W) & 0xFFu), qk, acc[o + 0]);              \
 	acc[o + 1] = __fmaf_rn((float)(((W) >> 8) & 0xFFu), qk, acc[o + 1]);       \
@@ -1119,22 +1159,24 @@ __global__ __launch_bounds__(THREADS) void k_prefilter_i8(
 	PF8_ACC4((V).y, qk, 4)                                                     \
 	PF8_ACC4((V).z, qk, 8)                                                     \
 	PF8_ACC4((V).w, qk, 12)
-		uint32_t kk = 0;
-		for (; kk + 8 <= d; kk += 8) {
-			uint4 w[8];
+		if (live) {
+			uint32_t kk = 0;
+			for (; kk + 8 <= d; kk += 8) {
+				uint4 w[8];
 #pragma unroll
-			for (uint32_t j = 0; j < 8; j++)
-				w[j] = *(const uint4 *)(p + (uint64_t)(kk + j) * sn_pad);
+				for (uint32_t j = 0; j < 8; j++)
+					w[j] = *(const uint4 *)(p + (uint64_t)(kk + j) * sn_pad);
 #pragma unroll
-			for (uint32_t j = 0; j < 8; j++) {
-				const float qk = qg[kk + j]; // uniform: scalar load
-				PF8_ACC(w[j], qk)
+				for (uint32_t j = 0; j < 8; j++) {
+					const float qk = qg[kk + j]; // uniform: scalar load
+					PF8_ACC(w[j], qk)
+				}
 			}
-		}
-		for (; kk < d; kk++) {
-			const uint4 w1 = *(const uint4 *)(p + (uint64_t)kk * sn_pad);
-			const float qk = qg[kk];
-			PF8_ACC(w1, qk)
+			for (; kk < d; kk++) {
+				const uint4 w1 = *(const uint4 *)(p + (uint64_t)kk * sn_pad);
+				const float qk = qg[kk];
+				PF8_ACC(w1, qk)
+			}
 		}
 #undef PF8_ACC
 #undef PF8_ACC4
@@ -1156,6 +1198,11 @@ __global__ __launch_bounds__(THREADS) void k_prefilter_i8(
 				        (__float_as_uint(a) & 0x7F800000u) != 0x7F800000u;
 				up[c] = ok[c] ? a + pe[j] : ninf;
 				lo[j] = ok[c] ? a - pe[j] : ninf;
+				if constexpr (MASKED) {
+					const bool allowed = (mb >> c) & 1u;
+					ok[c] = ok[c] && allowed;
+					lo[j] = allowed ? lo[j] : qnan;
+				}
 			}
 			*(float4 *)(scores + r0 + 4 * g) =
 			    make_float4(lo[0], lo[1], lo[2], lo[3]);
@@ -1412,6 +1459,9 @@ __global__ void k_shadow_i6(const float *__restrict__ cm,
 // bounds go to the block top-K, lower bounds to scores[], exactly as in
 // k_prefilter_i8. A block collects the rows of PF6_SWEEPS sweeps that beat
 // its current Kth upper bound, then runs one select: the same 17 KB buffer.
+// MASKED as in k_prefilter: lane = row, so a wave's 64 rows of one sweep are
+// exactly one mask word, and the skip is per wave and sweep.
+template <bool MASKED>
 __global__ __launch_bounds__(THREADS) void k_prefilter_i6(
     const uint4 *__restrict__ hp, const uint2 *__restrict__ lp,
     const float *__restrict__ pscale, const float *__restrict__ peps,
@@ -1419,7 +1469,7 @@ __global__ __launch_bounds__(THREADS) void k_prefilter_i6(
     uint32_t ngroups, const uint32_t *__restrict__ qd, float qscale,
     float qeps, uint32_t qbias, uint32_t k, uint64_t rows_per_block,
     float *__restrict__ scores, Cand *__restrict__ block_out,
-    uint32_t *__restrict__ cand_cnt) {
+    uint32_t *__restrict__ cand_cnt, const uint64_t *__restrict__ mask) {
 	__shared__ uint64_t buf[PF_TILE + MAX_K];
 	__shared__ uint64_t topk[MAX_K];
 	__shared__ int cnt;
@@ -1446,6 +1496,13 @@ __global__ __launch_bounds__(THREADS) void k_prefilter_i6(
 			const uint4 *ph = hp + r;
 			const uint2 *pl = lp + r;
 			uint32_t ah2 = 0, ah1 = 0, ah0 = 0, al2 = 0, al1 = 0, al0 = 0;
+			bool allowed = true, live = true;
+			if constexpr (MASKED) {
+				// sbase is a multiple of 256: r >> 6 is the wave's own word
+				const uint64_t mw = mask[r >> 6];
+				allowed = (mw >> (r & 63)) & 1ULL;
+				live = __ballot(mw != 0ULL) != 0ULL;
+			}
 #define PF6_DOT3(X, m, a2, a1, a0)                                             \
 	a2 = __builtin_amdgcn_udot8((X), qw[0 + (m)], a2, false);                  \
 	a1 = __builtin_amdgcn_udot8((X), qw[4 + (m)], a1, false);                  \
@@ -1462,25 +1519,27 @@ __global__ __launch_bounds__(THREADS) void k_prefilter_i6(
 		PF6_DOT3((LV).y & 0x33333333u, 2, al2, al1, al0)                       \
 		PF6_DOT3(((LV).y >> 2) & 0x33333333u, 3, al2, al1, al0)                \
 	}
-			uint32_t g = 0;
-			for (; g + PF6_UNROLL <= ngroups; g += PF6_UNROLL) {
-				pf6_v4 hv[PF6_UNROLL];
-				pf6_v2 lv[PF6_UNROLL];
+			if (live) {
+				uint32_t g = 0;
+				for (; g + PF6_UNROLL <= ngroups; g += PF6_UNROLL) {
+					pf6_v4 hv[PF6_UNROLL];
+					pf6_v2 lv[PF6_UNROLL];
 #pragma unroll
-				for (uint32_t j = 0; j < PF6_UNROLL; j++) {
-					hv[j] = __builtin_nontemporal_load(
-					    (const pf6_v4 *)(ph + (uint64_t)(g + j) * sn_pad));
-					lv[j] = __builtin_nontemporal_load(
-					    (const pf6_v2 *)(pl + (uint64_t)(g + j) * sn_pad));
+					for (uint32_t j = 0; j < PF6_UNROLL; j++) {
+						hv[j] = __builtin_nontemporal_load(
+						    (const pf6_v4 *)(ph + (uint64_t)(g + j) * sn_pad));
+						lv[j] = __builtin_nontemporal_load(
+						    (const pf6_v2 *)(pl + (uint64_t)(g + j) * sn_pad));
+					}
+#pragma unroll
+					for (uint32_t j = 0; j < PF6_UNROLL; j++)
+						PF6_GROUP(hv[j], lv[j], g + j)
 				}
-#pragma unroll
-				for (uint32_t j = 0; j < PF6_UNROLL; j++)
-					PF6_GROUP(hv[j], lv[j], g + j)
-			}
-			for (; g < ngroups; g++) {
-				const uint4 hv1 = ph[(uint64_t)g * sn_pad];
-				const uint2 lv1 = pl[(uint64_t)g * sn_pad];
-				PF6_GROUP(hv1, lv1, g)
+				for (; g < ngroups; g++) {
+					const uint4 hv1 = ph[(uint64_t)g * sn_pad];
+					const uint2 lv1 = pl[(uint64_t)g * sn_pad];
+					PF6_GROUP(hv1, lv1, g)
+				}
 			}
 #undef PF6_GROUP
 #undef PF6_DOT3
@@ -1492,9 +1551,14 @@ __global__ __launch_bounds__(THREADS) void k_prefilter_i6(
 			    1.0f, __fmul_rn(__fmul_rn((float)N, pscale[r]), qscale));
 			const float e =
 			    __fadd_rn(pe, __fmul_rn(__fadd_rn(1.0f, pe), qeps));
-			const bool ok = r < row_end &&
+			const bool ok = allowed && r < row_end &&
 			                (__float_as_uint(a) & 0x7F800000u) != 0x7F800000u;
-			scores[r] = ok ? __fsub_rn(a, e) : ninf;
+			if constexpr (MASKED)
+				scores[r] = ok        ? __fsub_rn(a, e)
+				            : allowed ? ninf
+				                      : __uint_as_float(0x7FC00000u);
+			else
+				scores[r] = ok ? __fsub_rn(a, e) : ninf;
 			if (ok) {
 				const uint64_t v =
 				    ((uint64_t)d_key32(__fadd_rn(a, e)) << 32) | (uint32_t)r;
@@ -3595,15 +3659,24 @@ static int knn_large_k(sdbv_ctx *ctx, Table &t, const float *q, uint32_t d,
 // flight per CU — 3.5 % of the kernel at 10M rows
 // (profiles/prefilter_scan.md).
 static uint64_t prefilter_grid(sdbv_ctx *ctx, uint64_t n, int kind,
-                               uint64_t *rows_per_block) {
-	uint64_t &slots = ctx->pf_slots[kind];
+                               bool masked, uint64_t *rows_per_block) {
+	uint64_t &slots = ctx->pf_slots[masked][kind];
 	if (slots == 0) {
 		int per_cu = 0, cus = 0;
 		const void *kernel = nullptr;
 		switch (kind) {
-		case 1: kernel = (const void *)k_prefilter; break;
-		case 2: kernel = (const void *)k_prefilter_i8; break;
-		case 3: kernel = (const void *)k_prefilter_i6; break;
+		case 1:
+			kernel = masked ? (const void *)k_prefilter<true>
+			                : (const void *)k_prefilter<false>;
+			break;
+		case 2:
+			kernel = masked ? (const void *)k_prefilter_i8<true>
+			                : (const void *)k_prefilter_i8<false>;
+			break;
+		case 3:
+			kernel = masked ? (const void *)k_prefilter_i6<true>
+			                : (const void *)k_prefilter_i6<false>;
+			break;
 		}
 		hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(
 		    &per_cu, kernel, THREADS, 0);
@@ -3635,15 +3708,46 @@ struct PfQ6 { // int6 tier: the quantised query's kernel operands
 
 static inline int shadow_kind(const Table &t) { return t.sh.kind; }
 
+// Upload the query for a call that may take the prefilter of tier kind (0:
+// none, the plain query): the int6 tier's digit words ride behind the query
+// in the same copy and *q6 receives its kernel operands; *qbias receives the
+// int8 tier's bias term 128 * sum q_k, one f64 sum rounded once.
+static int stage_query_pf(sdbv_ctx *ctx, const float *q, uint32_t d,
+                          double q_norm, int kind, PfQ6 *q6, float *qbias) {
+	size_t q_bytes = d * sizeof(float);
+	*qbias = 0.f;
+	if (kind == 3) {
+		const uint32_t G = (d + 31) / 32;
+		float sq, rho;
+		uint32_t qs;
+		pf_q12(q, d, q_norm, (uint32_t *)(ctx->q_pin + d), nullptr, &sq, &rho,
+		       &qs);
+		q_bytes += (size_t)G * PF6_QWORDS * sizeof(uint32_t);
+		q6->qscale = (float)((double)sq / q_norm);
+		q6->qeps = rho > 0.f ? pf_round_up_f32(1.01 * (double)rho) : 0.f;
+		q6->bias = 65536u * (32u * G) - 32u * qs;
+	} else if (kind == 2) {
+		double qsum = 0.0;
+		for (uint32_t i = 0; i < d; i++)
+			qsum += (double)q[i];
+		*qbias = (float)(128.0 * qsum);
+	}
+	return stage_query(ctx, q, d, q_bytes);
+}
+
 // The prefilter path of sdbv_knn_bruteforce (cosine, k <= MAX_K, table with
 // a shadow, query inside the norm window; q already in ctx->q_dev and the
 // query scratch sized for prefilter_grid). host_out[0..k) receives the
 // exact top-k, *ncand the candidate count; *ncand > PF_CAND_CAP means the
 // list overflowed and host_out is void: the caller runs the exact scan.
 // One D2H copy and one sync, like the exact path. Caller holds ctx->mu.
+// mask = nullptr for the unfiltered call; the filtered call passes the
+// device bitmap of upload_filter_mask (sn_pad / 64 words) and gets the
+// top-k of the allowed rows: the stream runs masked, everything behind it
+// is the same.
 static int knn_prefilter(sdbv_ctx *ctx, Table &t, uint32_t k, double q_norm,
-                         float qbias, const PfQ6 &q6, Cand *host_out,
-                         uint32_t *ncand) {
+                         float qbias, const PfQ6 &q6, const uint64_t *mask,
+                         Cand *host_out, uint32_t *ncand) {
 	const Shadow &sh = t.sh;
 	const int kind = sh.kind;
 	if (ctx->pf_scores_cap < sh.sn_pad) {
@@ -3663,7 +3767,8 @@ static int knn_prefilter(sdbv_ctx *ctx, Table &t, uint32_t k, double q_norm,
 		HIP_CHECK(ctx, hipMalloc(&ctx->pf_res, (MAX_K + 2) * sizeof(Cand)));
 
 	uint64_t rows_per_block = 0;
-	uint64_t nblocks = prefilter_grid(ctx, t.n, kind, &rows_per_block);
+	uint64_t nblocks =
+	    prefilter_grid(ctx, t.n, kind, mask != nullptr, &rows_per_block);
 	Cand *res = (Cand *)ctx->pf_res;
 	// device counter: behind the k results and the copy of the count that
 	// k_pf_final appends to them
@@ -3671,33 +3776,37 @@ static int knn_prefilter(sdbv_ctx *ctx, Table &t, uint32_t k, double q_norm,
 	const float inv_q = (float)(1.0 / q_norm);
 
 	HIP_CHECK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+#define LAUNCH_PF(KERNEL, ...)                                                 \
+	do {                                                                       \
+		if (mask)                                                              \
+			hipLaunchKernelGGL(KERNEL<true>, dim3((uint32_t)nblocks),          \
+			                   dim3(THREADS), 0, ctx->stream, __VA_ARGS__,     \
+			                   rows_per_block, ctx->pf_scores,                 \
+			                   (Cand *)ctx->block_out, cand_cnt, mask);        \
+		else                                                                   \
+			hipLaunchKernelGGL(KERNEL<false>, dim3((uint32_t)nblocks),         \
+			                   dim3(THREADS), 0, ctx->stream, __VA_ARGS__,     \
+			                   rows_per_block, ctx->pf_scores,                 \
+			                   (Cand *)ctx->block_out, cand_cnt, mask);        \
+	} while (0)
 	switch (kind) {
 	case 1:
-		hipLaunchKernelGGL(k_prefilter, dim3((uint32_t)nblocks), dim3(THREADS),
-		                   0, ctx->stream, (const uint16_t *)sh.codes,
-		                   sh.pinv(), t.n, sh.sn_pad, t.d, ctx->q_dev, inv_q, k,
-		                   rows_per_block, ctx->pf_scores,
-		                   (Cand *)ctx->block_out, cand_cnt);
+		LAUNCH_PF(k_prefilter, (const uint16_t *)sh.codes, sh.pinv(), t.n,
+		          sh.sn_pad, t.d, ctx->q_dev, inv_q, k);
 		break;
 	case 2:
-		hipLaunchKernelGGL(k_prefilter_i8, dim3((uint32_t)nblocks),
-		                   dim3(THREADS), 0, ctx->stream,
-		                   (const uint8_t *)sh.codes, sh.pscale(), sh.peps(),
-		                   t.n, sh.sn_pad, t.d, ctx->q_dev, inv_q, qbias, k,
-		                   rows_per_block, ctx->pf_scores,
-		                   (Cand *)ctx->block_out, cand_cnt);
+		LAUNCH_PF(k_prefilter_i8, (const uint8_t *)sh.codes, sh.pscale(),
+		          sh.peps(), t.n, sh.sn_pad, t.d, ctx->q_dev, inv_q, qbias, k);
 		break;
 	case 3:
-		hipLaunchKernelGGL(k_prefilter_i6, dim3((uint32_t)nblocks),
-		                   dim3(THREADS), 0, ctx->stream,
-		                   (const uint4 *)sh.plane_h(),
-		                   (const uint2 *)sh.plane_l(t.d), sh.pscale(),
-		                   sh.peps(), sh.xsum(), t.n, sh.sn_pad,
-		                   (t.d + 31) / 32, (const uint32_t *)(ctx->q_dev + t.d),
-		                   q6.qscale, q6.qeps, q6.bias, k, rows_per_block,
-		                   ctx->pf_scores, (Cand *)ctx->block_out, cand_cnt);
+		LAUNCH_PF(k_prefilter_i6, (const uint4 *)sh.plane_h(),
+		          (const uint2 *)sh.plane_l(t.d), sh.pscale(), sh.peps(),
+		          sh.xsum(), t.n, sh.sn_pad, (t.d + 31) / 32,
+		          (const uint32_t *)(ctx->q_dev + t.d), q6.qscale, q6.qeps,
+		          q6.bias, k);
 		break;
 	}
+#undef LAUNCH_PF
 	HIP_CHECK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
 	// K smallest approximate distances (int8, int6: upper bounds) ->
 	// final_out (A_K, or U_K, = entry k-1)
@@ -3738,7 +3847,8 @@ static int knn_prefilter(sdbv_ctx *ctx, Table &t, uint32_t k, double q_norm,
 	(void)hipEventElapsedTime(&ms_final, ctx->ev3, ctx->ev4);
 	ctx->stats.last_scan_kernel_ms = (double)ms_pre + ms_rescore;
 	ctx->stats.last_merge_kernel_ms = (double)ms_sel + ms_final;
-	ctx->stats.last_rows_scanned = t.n;
+	if (!mask) // the filtered call keeps its allowed-row count
+		ctx->stats.last_rows_scanned = t.n;
 	return SDBV_OK;
 }
 
@@ -3791,7 +3901,8 @@ int sdbv_knn_bruteforce(sdbv_ctx *ctx, uint64_t table, const float *q,
 	const int kind = shadow_kind(t);
 	uint64_t pf_rows_per_block = 0;
 	uint64_t scratch_blocks = std::max(
-	    nblocks, kind ? prefilter_grid(ctx, t.n, kind, &pf_rows_per_block) : 0);
+	    nblocks,
+	    kind ? prefilter_grid(ctx, t.n, kind, false, &pf_rows_per_block) : 0);
 	int rc = ensure_query_scratch(ctx, d, scratch_blocks, k);
 	if (rc != SDBV_OK)
 		return rc;
@@ -3802,35 +3913,18 @@ int sdbv_knn_bruteforce(sdbv_ctx *ctx, uint64_t table, const float *q,
 	// overflowed, takes the exact scan; results never depend on the choice.
 	const bool use_pf =
 	    kind != 0 && q_norm >= PF_NORM_MIN && q_norm <= PF_NORM_MAX;
-	size_t q_bytes = d * sizeof(float);
 	PfQ6 q6;
-	if (use_pf && kind == 3) {
-		// int6 tier: the query's digit words ride behind it in the same copy
-		const uint32_t G = (d + 31) / 32;
-		float sq, rho;
-		uint32_t qs;
-		pf_q12(q, d, q_norm, (uint32_t *)(ctx->q_pin + d), nullptr, &sq, &rho,
-		       &qs);
-		q_bytes += (size_t)G * PF6_QWORDS * sizeof(uint32_t);
-		q6.qscale = (float)((double)sq / q_norm);
-		q6.qeps = rho > 0.f ? pf_round_up_f32(1.01 * (double)rho) : 0.f;
-		q6.bias = 65536u * (32u * G) - 32u * qs;
-	}
-	rc = stage_query(ctx, q, d, q_bytes);
+	float qbias = 0.f;
+	rc = stage_query_pf(ctx, q, d, q_norm, use_pf ? kind : 0, &q6, &qbias);
 	if (rc != SDBV_OK)
 		return rc;
 
 	auto t_start = std::chrono::steady_clock::now();
 	Cand host_out[MAX_K + 1];
 	if (use_pf) {
-		// int8 tier: the bias term 128 * sum q_k, one f64 sum rounded once
-		double qsum = 0.0;
-		if (kind == 2)
-			for (uint32_t i = 0; i < d; i++)
-				qsum += (double)q[i];
 		uint32_t ncand = 0;
-		rc = knn_prefilter(ctx, t, k, q_norm, (float)(128.0 * qsum), q6,
-		                   host_out, &ncand);
+		rc = knn_prefilter(ctx, t, k, q_norm, qbias, q6, nullptr, host_out,
+		                   &ncand);
 		if (rc != SDBV_OK)
 			return rc;
 		ctx->stats.last_prefilter_candidates = ncand;
@@ -3903,15 +3997,23 @@ static uint64_t filter_rowlist_max() {
 	return cap;
 }
 
-// Masked scan of the filtered call: upload the bitmap (tail cleared,
-// zero-filled to n_pad / 64 words), k_scan<., true> over scan_grid, the
-// merge tree. q already in ctx->q_dev, scratch sized for nblocks. Caller
-// holds ctx->mu.
-static int knn_masked_scan(sdbv_ctx *ctx, Table &t, uint32_t k, double q_norm,
-                           const uint64_t *allow, uint64_t allow_words,
-                           uint64_t nblocks, uint64_t rows_per_block,
-                           Cand *host_out) {
-	const uint64_t mwords = t.n_pad / 64;
+// SDBV_FILTER_PREFILTER / SDBV_FILTER_PREFILTER_MIN_ROWS, read at each call:
+// whether a filtered call on this shadowed table may stream the shadow. The
+// default minimum is the unfiltered tiers' stream-vs-fixed-cost crossover,
+// the smallest table that gets a shadow by policy.
+static bool filter_prefilter_policy(const Table &t) {
+	return shadow_policy(&t, "SDBV_FILTER_PREFILTER",
+	                     "SDBV_FILTER_PREFILTER_MIN_ROWS", PF_DEFAULT_MIN_ROWS);
+}
+
+// Upload the bitmap of the filtered call to ctx->flt_mask, once per call:
+// pinned copy, tail of the last word cleared, zero-filled behind it, one H2D
+// copy. The buffers hold max(n_pad, sn_pad) / 64 words: k_scan<., true>
+// reads words below n_pad / 64, the masked prefilter kernels address rows up
+// to the shadow's sn_pad >= n_pad.
+static int upload_filter_mask(sdbv_ctx *ctx, const Table &t,
+                              const uint64_t *allow, uint64_t allow_words) {
+	const uint64_t mwords = std::max(t.n_pad, t.sh.kind ? t.sh.sn_pad : 0) / 64;
 	if (ctx->flt_mask_cap < mwords) {
 		if (ctx->flt_mask)
 			(void)hipFree(ctx->flt_mask);
@@ -3933,6 +4035,15 @@ static int knn_masked_scan(sdbv_ctx *ctx, Table &t, uint32_t k, double q_norm,
 	HIP_CHECK(ctx, hipMemcpyAsync(ctx->flt_mask, ctx->flt_mask_pin,
 	                              mwords * sizeof(uint64_t),
 	                              hipMemcpyHostToDevice, ctx->stream));
+	return SDBV_OK;
+}
+
+// Masked scan of the filtered call: k_scan<., true> over scan_grid under the
+// bitmap upload_filter_mask left in ctx->flt_mask, then the merge tree. q
+// already in ctx->q_dev, scratch sized for nblocks. Caller holds ctx->mu.
+static int knn_masked_scan(sdbv_ctx *ctx, Table &t, uint32_t k, double q_norm,
+                           uint64_t nblocks, uint64_t rows_per_block,
+                           Cand *host_out) {
 	HIP_CHECK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
 	launch_scan(ctx, t, k, q_norm, nblocks, rows_per_block, ctx->flt_mask);
 	HIP_CHECK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
@@ -4020,30 +4131,64 @@ int sdbv_knn_bruteforce_filtered(sdbv_ctx *ctx, uint64_t table, const float *q,
 		return knn_large_k(ctx, t, q, d, k, allow, out_ids, out_dists, out_n);
 
 	const bool by_list = count <= list_max;
-	// the masked scan runs on k_scan's grid
+	double q_norm = sqrt((double)h_sumsq_f32(q, d));
+	// Shadow path: more allowed rows than the list serves,
+	// a shadowed (hence cosine) table the policy admits, and a query inside
+	// the norm window the bounds are proven for. Everything else, and a call
+	// whose candidate list overflowed, takes the path it took before;
+	// results never depend on the choice.
+	const int kind = shadow_kind(t);
+	const bool use_pf = !by_list && kind != 0 && q_norm >= PF_NORM_MIN &&
+	                    q_norm <= PF_NORM_MAX && filter_prefilter_policy(t);
+	// the masked scan runs on k_scan's grid; block_out serves whichever of
+	// the two grids runs, since an overflow reruns the masked scan
 	uint64_t rows_per_block = 0;
 	const uint64_t nblocks = scan_grid(t.n, &rows_per_block);
-	int rc = ensure_query_scratch(ctx, d, by_list ? 1 : nblocks, k);
+	uint64_t pf_rows_per_block = 0;
+	const uint64_t scratch_blocks = std::max(
+	    nblocks,
+	    use_pf ? prefilter_grid(ctx, t.n, kind, true, &pf_rows_per_block) : 0);
+	int rc = ensure_query_scratch(ctx, d, by_list ? 1 : scratch_blocks, k);
 	if (rc != SDBV_OK)
 		return rc;
-	double q_norm = sqrt((double)h_sumsq_f32(q, d));
-	rc = stage_query(ctx, q, d, d * sizeof(float));
+	PfQ6 q6;
+	float qbias = 0.f;
+	rc = stage_query_pf(ctx, q, d, q_norm, use_pf ? kind : 0, &q6, &qbias);
 	if (rc != SDBV_OK)
 		return rc;
-	Cand host_out[MAX_K];
-	if (by_list)
-		rc = knn_row_list(ctx, t, k, q_norm, (uint32_t)count, host_out);
-	else
-		rc = knn_masked_scan(ctx, t, k, q_norm, allow, allow_words, nblocks,
-		                     rows_per_block, host_out);
-	if (rc != SDBV_OK)
-		return rc;
-	float ms_scan = 0, ms_merge = 0;
-	(void)hipEventElapsedTime(&ms_scan, ctx->ev0, ctx->ev1);
-	(void)hipEventElapsedTime(&ms_merge, ctx->ev1, ctx->ev2);
-	ctx->stats.last_scan_kernel_ms = ms_scan;
-	ctx->stats.last_merge_kernel_ms = ms_merge;
-	ctx->stats.last_scan_path = by_list ? 8u : 7u;
+	if (!by_list) {
+		rc = upload_filter_mask(ctx, t, allow, allow_words);
+		if (rc != SDBV_OK)
+			return rc;
+	}
+	Cand host_out[MAX_K + 1];
+	if (use_pf) {
+		uint32_t ncand = 0;
+		rc = knn_prefilter(ctx, t, k, q_norm, qbias, q6, ctx->flt_mask,
+		                   host_out, &ncand);
+		if (rc != SDBV_OK)
+			return rc;
+		ctx->stats.last_prefilter_candidates = ncand;
+		ctx->stats.last_scan_path = (ncand <= PF_CAND_CAP ? 9u : 10u) +
+		                            2u * (uint32_t)(kind - 1);
+	}
+	if (!(ctx->stats.last_scan_path & 1u)) {
+		// no shadow pass, or one that overflowed: the mask is on the device
+		if (by_list)
+			rc = knn_row_list(ctx, t, k, q_norm, (uint32_t)count, host_out);
+		else
+			rc = knn_masked_scan(ctx, t, k, q_norm, nblocks, rows_per_block,
+			                     host_out);
+		if (rc != SDBV_OK)
+			return rc;
+		float ms_scan = 0, ms_merge = 0;
+		(void)hipEventElapsedTime(&ms_scan, ctx->ev0, ctx->ev1);
+		(void)hipEventElapsedTime(&ms_merge, ctx->ev1, ctx->ev2);
+		ctx->stats.last_scan_kernel_ms = ms_scan;
+		ctx->stats.last_merge_kernel_ms = ms_merge;
+		if (!use_pf)
+			ctx->stats.last_scan_path = by_list ? 8u : 7u;
+	}
 	ctx->stats.last_total_ms =
 	    std::chrono::duration<double, std::milli>(
 	        std::chrono::steady_clock::now() - t_start)
