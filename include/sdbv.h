@@ -100,10 +100,19 @@ typedef struct sdbv_stats {
 	                            prefilter under the bitmap, 10 = that
 	                            overflowed, then masked scan, 11 / 12 = the
 	                            same for int8, 13 / 14 for int6, 0 = the
-	                            all-distances route */
+	                            all-distances route. sdbv_knn_bruteforce
+	                            again: 15 = two-stage int6 prefilter (plane H
+	                            streamed alone, survivors refined with plane
+	                            L), 16 = its candidate list overflowed, then
+	                            exact scan */
 	uint64_t last_filter_rows; /* allowed rows of the last filtered call (for
 	                              such a call last_rows_scanned is the same
 	                              count) */
+	uint64_t last_prefilter_stage1; /* rows that passed the H-only test of the
+	                                   last two-stage call, also when that
+	                                   list overflowed and the plain int6
+	                                   path served the call (path 5 / 6);
+	                                   0 on every other path */
 } sdbv_stats;
 
 /* Create a context on HIP device `device` (-1 = current device). */
@@ -135,6 +144,11 @@ int sdbv_get_stats(sdbv_ctx *, sdbv_stats *out);
  * rounded up to a multiple of 32), if it also has at least
  * SDBV_SCAN_PREFILTER_I6_MIN_ROWS rows (environment, default 500000,
  * independent of the other thresholds) and SDBV_SCAN_PREFILTER_I6 is not 0.
+ * An int6 shadow that staging builds for a table of at least
+ * SDBV_SCAN_PREFILTER_H4_MIN_ROWS rows (environment, default 1000000) while
+ * SDBV_SCAN_PREFILTER_H4 is not 0 carries 8 B per row more: the bound and
+ * the code sum of its high-nibble plane read on its own, which the two-stage
+ * path needs (see sdbv_knn_bruteforce).
  * A table holds at
  * most one shadow. The shadow never changes a result (see
  * sdbv_knn_bruteforce). Tables staged for graph search (sdbv_hnsw_finalize,
@@ -165,7 +179,9 @@ int sdbv_table_set_prefilter(sdbv_ctx *, uint64_t table, int on);
 int sdbv_table_set_prefilter_kind(sdbv_ctx *, uint64_t table, int kind);
 /* Give the table the int6 shadow (codes in [-31, 31], one f32 scale, the
  * row's bound and the sum of its stored codes: 0.75 * d_pad + 12 B per row),
- * freeing a shadow of another kind. Errors as for
+ * freeing a shadow of another kind; without the side data of the two-stage
+ * path, which only staging builds (a staged int6 shadow that carries it is
+ * rebuilt without). Errors as for
  * sdbv_table_set_prefilter; free it with sdbv_table_set_prefilter(.., 0) or
  * sdbv_table_set_prefilter_kind(.., 0). */
 int sdbv_table_set_prefilter_i6(sdbv_ctx *, uint64_t table);
@@ -194,6 +210,16 @@ int sdbv_prefilter_i8_row(const float *x, uint32_t d, double norm,
 int sdbv_prefilter_i6_row(const float *x, uint32_t d, double norm,
                           int8_t *codes, float *scale, float *eps,
                           uint32_t *xsum);
+/* Host-only: the int6 row's high nibbles as the two-stage path reads them.
+ * codes_h[k] = (code + 32) >> 2 in [0, 15] of sdbv_prefilter_i6_row's codes,
+ * standing for scale * (4 * codes_h[k] + 1.5 - 32); *xsum_h = sum of
+ * codes_h over the row padded with nibbles 8 to a multiple of 32 features;
+ * *eps4 = the proven bound of THIS row for that approximant, used as *eps is
+ * (e = eps4 + (1 + eps4) * qeps). Uncovered rows: nibbles 8, *scale = NaN,
+ * *eps4 = 0. */
+int sdbv_prefilter_h4_row(const float *x, uint32_t d, double norm,
+                          uint8_t *codes_h, float *scale, float *eps4,
+                          uint32_t *xsum_h);
 /* Host-only: quantise one query of d <= 4096 f32 elements for the int6 tier
  * exactly as sdbv_knn_bruteforce does. codes[k] = rint(q[k] / sq) in
  * [-2047, 2047], *sq = f32(maxabs / 2047), *rho_q = |q - sq * codes| / |q|
@@ -237,7 +263,20 @@ void sdbv_gen_f32(uint64_t seed, uint64_t row0, uint64_t nrows, uint32_t d,
  * quantisation error is part of each row's bound. It recomputes those rows with the exact chain. Exactness guarantee: ids and distance bits equal the exact scan's
  * for every input — rows the bound cannot cover are always recomputed, and
  * a query with more than 16384 candidates reruns the exact scan
- * (sdbv_stats.last_scan_path tells which path ran). */
+ * (sdbv_stats.last_scan_path tells which path ran).
+ *
+ * Two-stage int6 path (last_scan_path 15), chosen at each call over an int6
+ * shadow that carries the H-only side data, unless SDBV_SCAN_PREFILTER_H4 is
+ * 0 or the table has fewer than SDBV_SCAN_PREFILTER_H4_MIN_ROWS rows
+ * (default 1000000, the measured crossover): the
+ * call streams the high-nibble plane alone (two thirds of the int6 bytes),
+ * takes the threshold T from the EXACT distances of the K rows with the
+ * smallest upper bounds, lists the rows whose H-only lower bound is not
+ * above T (at most SDBV_SCAN_PREFILTER_H4_LIST_MAX of them, default and
+ * ceiling 262144, read at each call), keeps of those the rows whose full
+ * int6 lower bound is not above T, and recomputes these. A first list that
+ * overflows hands the call to the plain int6 path (5 / 6); more than 16384
+ * rows after the second test rerun the exact scan (16). */
 int sdbv_knn_bruteforce(sdbv_ctx *, uint64_t table, const float *q, uint32_t d,
                         uint32_t k, uint64_t *out_ids, double *out_dists,
                         uint32_t *out_n);

@@ -55,6 +55,7 @@ class _Stats(ctypes.Structure):
         ("last_prefilter_candidates", ctypes.c_uint64),
         ("last_scan_path", ctypes.c_uint32),
         ("last_filter_rows", ctypes.c_uint64),
+        ("last_prefilter_stage1", ctypes.c_uint64),
     ]
 
 
@@ -96,6 +97,9 @@ def lib():
                                         f32p]
     L.sdbv_prefilter_i6_row.argtypes = [f32p, u32, ctypes.c_double,
                                         ctypes.POINTER(ctypes.c_int8), f32p,
+                                        f32p, ctypes.POINTER(ctypes.c_uint32)]
+    L.sdbv_prefilter_h4_row.argtypes = [f32p, u32, ctypes.c_double,
+                                        ctypes.POINTER(ctypes.c_uint8), f32p,
                                         f32p, ctypes.POINTER(ctypes.c_uint32)]
     L.sdbv_prefilter_q12.argtypes = [f32p, u32,
                                      ctypes.POINTER(ctypes.c_int16), f32p,
@@ -451,6 +455,26 @@ def prefilter_i6_row(x, norm):
         ctypes.byref(scale), ctypes.byref(eps), ctypes.byref(xsum)),
         "sdbv_prefilter_i6_row")
     return codes, np.float32(scale.value), np.float32(eps.value), xsum.value
+
+
+def prefilter_h4_row(x, norm):
+    """The int6 shadow row's high nibbles as the two-stage prefilter reads
+    them (host-only): (codes_h uint8[d] in [0, 15], scale f32, eps4 f32,
+    xsum_h). codes_h[k] stands for scale * (4 * codes_h[k] + 1.5 - 32);
+    xsum_h is their sum over the row padded with nibbles 8 to a multiple of
+    32 features; scale is NaN for a row the bound cannot cover."""
+    import numpy as np
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    codes = np.empty(x.size, dtype=np.uint8)
+    scale = ctypes.c_float(0.0)
+    eps4 = ctypes.c_float(0.0)
+    xsum_h = ctypes.c_uint32(0)
+    _check(None, lib().sdbv_prefilter_h4_row(
+        x.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), x.size, float(norm),
+        codes.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
+        ctypes.byref(scale), ctypes.byref(eps4), ctypes.byref(xsum_h)),
+        "sdbv_prefilter_h4_row")
+    return codes, np.float32(scale.value), np.float32(eps4.value), xsum_h.value
 
 
 def prefilter_q12(q):

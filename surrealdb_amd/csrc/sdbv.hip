@@ -89,9 +89,12 @@
 //  3 int6: 6-bit codes, bias 32, lane = row, features in groups of 32,
 //    G = ceil(d / 32); codes = plane H [G][sn_pad][4 dwords] with the high
 //    nibbles, then plane L [G][sn_pad][2 dwords] with the low pairs; side =
-//    pscale, peps, then xsum (the row's sum of stored codes).
+//    pscale, peps, then xsum (the row's sum of stored codes); with h4 also
+//    peps4 and xsum_h, the bound and the code sum of plane H read on its own
+//    (the two-stage path).
 struct Shadow {
 	int kind = 0;          // 0 none, 1 bf16, 2 int8, 3 int6
+	bool h4 = false;       // int6 only: side holds peps4 and xsum_h too
 	void *codes = nullptr; // owning
 	float *side = nullptr; // owning: sn_pad floats per side array
 	uint64_t sn_pad = 0;   // n rounded up to the tier's tile
@@ -100,6 +103,10 @@ struct Shadow {
 	float *pscale() const { return side; }
 	float *peps() const { return side + sn_pad; }
 	uint32_t *xsum() const { return (uint32_t *)(side + 2 * sn_pad); }
+	float *peps4() const { return h4 ? side + 3 * sn_pad : nullptr; }
+	uint32_t *xsum_h() const {
+		return h4 ? (uint32_t *)(side + 4 * sn_pad) : nullptr;
+	}
 	uint32_t *plane_h() const { return (uint32_t *)codes; }
 	uint32_t *plane_l(uint32_t d) const {
 		return plane_h() + (uint64_t)((d + 31) / 32) * sn_pad * 4;
@@ -141,9 +148,13 @@ struct sdbv_ctx {
 	float *pf_scores = nullptr; // [sn_pad] approximate distances
 	uint64_t pf_scores_cap = 0;
 	uint32_t *pf_rows = nullptr; // [PF_CAND_CAP] candidate rows
+	uint32_t *pf4_list = nullptr; // [PF4_LIST_CAP] rows that passed the H-only
+	                              // test of the two-stage path
+	void *pf4_thr = nullptr;      // [MAX_K] Cand: its threshold rows, exact
 	void *pf_cands = nullptr;    // [PF_CAND_CAP] rescored Cand
 	void *pf_res = nullptr;      // [MAX_K + 2] Cand: top-k, the count, counter
-	uint64_t pf_slots[2][4] = {}; // by MASKED and Shadow::kind: blocks of that
+	uint64_t pf_slots[2][5] = {}; // by MASKED and Shadow::kind (4 = the int6
+	                              // tier's H-only stream): blocks of that
 	                              // prefilter kernel the device holds at once
 	// batched path
 	rocblas_handle blas = nullptr;
@@ -1254,6 +1265,9 @@ __global__ __launch_bounds__(THREADS) void k_prefilter_i8(
 #define PF6_TILE (THREADS * PF6_SWEEPS) /* 2048 rows per select feed */
 #define PF6_QWORDS 12 /* query digit dwords per group: [3 digits][4 dwords] */
 #define PF6_UNROLL 6  /* groups in flight per lane: 9 KiB per wave */
+#ifndef PF4_UNROLL
+#define PF4_UNROLL 8 /* the H-only stream: 8 KiB per wave */
+#endif
 typedef uint32_t pf6_v4 __attribute__((ext_vector_type(4)));
 typedef uint32_t pf6_v2 __attribute__((ext_vector_type(2)));
 
@@ -1309,10 +1323,34 @@ __host__ __device__ static inline float pf_round_up_f32(double e) {
 //    1 / (2047 sqrt(d)).
 // eps = 1.01 (rho_x + 1.001 (d + 8) u) + 2^-19, evaluated in f64 and rounded
 // UP to f32; the query term (1 + eps) qeps is added by the kernel.
+//
+// Plane H on its own (the two-stage path, k_prefilter_i6<false, true>): with
+// h_k = xu_k >> 2 the approximant of x_k is x^4_k = scale (4 h_k + 1.5 - 32)
+// = scale (8 h_k - 61) / 2; the centre 1.5 of the dropped pair halves the
+// truncation residual. N4 = sum (8 h_k - 61) cq_k is an exact integer,
+// computed as 8 sum h_k qu_k - 8 * 2048 xsum_h - 61 sum cq_k with xsum_h =
+// sum h_k over the padded row (padding features hold h = 8 against cq = 0 and
+// add nothing to N4) and the last term a per-query constant;
+// approx = 1 - f32(N4) * (pscale / 2) * qscale. Ranges: sum h qu <=
+// 15 * 4095 * 4096 < 2^28; 8 h - 61 lies in [-61, 59], so |N4| <=
+// 61 * 2047 * 4096 < 2^30 fits int32 and every partial result taken mod 2^32
+// is harmless; pscale / 2 is exact in f32 (pscale >= 1 / (31 sqrt(d)), far
+// from the subnormals). The proof above carries over with x^4 for x^ and
+// rho4 = |x - x^4| / |x|, the row's actual residual, for rho_x; only the
+// finish differs, since an element is within 2 scale of its approximant and
+// rho4 can reach 2 sqrt(d) / 31 = 4.2 at MAX_D. While rho4 <= 1.04 every
+// rounded value is below the one the count above used and the 2^-19 holds as
+// it stands. Beyond, every rounded value is below 6 (1 + rho4) <= 32 and the
+// 14 roundings add up to less than 450 u < 2.7e-5, while the factor 1.01
+// needs 1.0005 for the norms and leaves 0.0095 rho4 > 9.8e-3 unused.
+// eps4 = 1.01 (rho4 + 1.001 (d + 8) u) + 2^-19, rounded UP to f32; an
+// uncovered row gets eps4 = 0 and xsum_h = 8 d_pad with its neutral codes.
+// eps4 and xsum_h may be null together: then neither is computed.
 __host__ __device__ static inline void pf_i6_row(
     const float *x, uint64_t xstride, uint32_t d, double norm, uint32_t *h,
     uint64_t hstride, uint32_t *l, uint64_t lstride, float *scale,
-    float *pscale, float *eps, uint32_t *xsum) {
+    float *pscale, float *eps, uint32_t *xsum, float *eps4 = nullptr,
+    uint32_t *xsum_h = nullptr) {
 	const uint32_t G = (d + 31) / 32;
 	float m = 0.f;
 	bool bad = false;
@@ -1327,8 +1365,8 @@ __host__ __device__ static inline void pf_i6_row(
 	const float sc = covered ? (float)((double)m / 31.0)
 	                         : __builtin_bit_cast(float, 0x7FC00000u);
 	const double sd = (double)sc;
-	double res2 = 0.0;
-	uint32_t xs = 0;
+	double res2 = 0.0, res4 = 0.0;
+	uint32_t xs = 0, xsh = 0;
 	for (uint32_t g = 0; g < G; g++) {
 		uint32_t hw[4] = {0, 0, 0, 0}, lw[2] = {0, 0};
 #pragma unroll
@@ -1342,8 +1380,14 @@ __host__ __device__ static inline void pf_i6_row(
 				const double r = xv - sd * c;
 				res2 += r * r;
 				xu = (uint32_t)((int)c + 32);
+				if (eps4) {
+					const double r4 =
+					    xv - sd * ((double)(4 * (xu >> 2)) + 1.5 - 32.0);
+					res4 += r4 * r4;
+				}
 			}
 			xs += xu;
+			xsh += xu >> 2;
 			hw[i >> 3] |= (xu >> 2) << (4 * (i & 7));
 			const uint32_t f = i & 15;
 			lw[i >> 4] |= (xu & 3u) << (2 * (f < 8 ? 2 * f : 2 * (f - 8) + 1));
@@ -1355,6 +1399,10 @@ __host__ __device__ static inline void pf_i6_row(
 	}
 	*xsum = xs;
 	*scale = sc;
+	if (eps4) {
+		*xsum_h = xsh;
+		*eps4 = 0.f;
+	}
 	if (!covered) {
 		*pscale = sc;
 		*eps = 0.f;
@@ -1365,6 +1413,11 @@ __host__ __device__ static inline void pf_i6_row(
 	    1.01 * (rho + 1.001 * (double)(d + 8) * 0x1p-24) + 0x1p-19;
 	*pscale = (float)(sd / norm);
 	*eps = pf_round_up_f32(e);
+	if (eps4) {
+		const double rho4 = sqrt(res4) / norm * (1.0 + 0x1p-40);
+		*eps4 = pf_round_up_f32(
+		    1.01 * (rho4 + 1.001 * (double)(d + 8) * 0x1p-24) + 0x1p-19);
+	}
 }
 
 // Quantise a query for the int6 tier (host, once per call; q finite with a
@@ -1415,24 +1468,28 @@ static void pf_q12(const float *q, uint32_t d, double q_norm, uint32_t *words,
 	*rho = r > 0.0 ? pf_round_up_f32(r) : 0.f;
 }
 
-// Build the int6 shadow: one lane per row, as k_shadow_i8.
+// Build the int6 shadow: one lane per row, as k_shadow_i8. peps4 and xsum_h
+// are null for a shadow without the H-only side data.
 __global__ void k_shadow_i6(const float *__restrict__ cm,
                             const double *__restrict__ norms,
                             uint32_t *__restrict__ hp,
                             uint32_t *__restrict__ lp,
                             float *__restrict__ pscale,
                             float *__restrict__ peps,
-                            uint32_t *__restrict__ xsum, uint64_t n,
+                            uint32_t *__restrict__ xsum,
+                            float *__restrict__ peps4,
+                            uint32_t *__restrict__ xsum_h, uint64_t n,
                             uint64_t n_pad, uint64_t sn_pad, uint32_t d) {
 	const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
 	if (r >= sn_pad)
 		return;
 	const uint32_t G = (d + 31) / 32;
-	float sc, ps = __uint_as_float(0x7FC00000u), pe = 0.f;
-	uint32_t xs = 32u * 32u * G;
+	float sc, ps = __uint_as_float(0x7FC00000u), pe = 0.f, pe4 = 0.f;
+	uint32_t xs = 32u * 32u * G, xsh = 8u * 32u * G;
 	if (r < n) {
 		pf_i6_row(cm + r, n_pad, d, norms[r], hp + r * 4, sn_pad * 4,
-		          lp + r * 2, sn_pad * 2, &sc, &ps, &pe, &xs);
+		          lp + r * 2, sn_pad * 2, &sc, &ps, &pe, &xs,
+		          peps4 ? &pe4 : nullptr, &xsh);
 	} else { // padding row: never covered
 		for (uint32_t g = 0; g < G; g++) {
 			*(uint4 *)(hp + ((uint64_t)g * sn_pad + r) * 4) = make_uint4(
@@ -1443,6 +1500,10 @@ __global__ void k_shadow_i6(const float *__restrict__ cm,
 	pscale[r] = ps;
 	peps[r] = pe;
 	xsum[r] = xs;
+	if (peps4) { // the H-only side data (Shadow::h4)
+		peps4[r] = pe4;
+		xsum_h[r] = xsh;
+	}
 }
 
 // k_prefilter over the int6 shadow: one row per lane and sweep, one 16-byte
@@ -1461,7 +1522,50 @@ __global__ void k_shadow_i6(const float *__restrict__ cm,
 // its current Kth upper bound, then runs one select: the same 17 KB buffer.
 // MASKED as in k_prefilter: lane = row, so a wave's 64 rows of one sweep are
 // exactly one mask word, and the skip is per wave and sweep.
-template <bool MASKED>
+//
+// H4 (the two-stage path's stream, unmasked only): plane H alone, one
+// non-temporal 16-byte load per group and lane, PF4_UNROLL groups in flight,
+// three accumulators. lp is never read (nullptr); peps is the shadow's peps4,
+// xsum its xsum_h and qbias = -61 sum cq (mod 2^32). N4 = 8 (256 A_h2 +
+// 16 A_h1 + A_h0) - 8 * 2048 xsum_h + qbias and a = 1 - f32(N4) *
+// (pscale / 2) * qscale (ranges and bound above pf_i6_row). Block 0 also
+// clears the first list's counter, cand_cnt[1], for k_pf4_compact.
+#define PF6_DOT3(X, m, a2, a1, a0)                                             \
+	a2 = __builtin_amdgcn_udot8((X), qw[0 + (m)], a2, false);                  \
+	a1 = __builtin_amdgcn_udot8((X), qw[4 + (m)], a1, false);                  \
+	a0 = __builtin_amdgcn_udot8((X), qw[8 + (m)], a0, false);
+#define PF6_GROUP_H(HV, gi)                                                    \
+	{                                                                          \
+		const uint32_t *qw = qd + (uint64_t)(gi) * PF6_QWORDS;                 \
+		PF6_DOT3((HV).x, 0, ah2, ah1, ah0)                                     \
+		PF6_DOT3((HV).y, 1, ah2, ah1, ah0)                                     \
+		PF6_DOT3((HV).z, 2, ah2, ah1, ah0)                                     \
+		PF6_DOT3((HV).w, 3, ah2, ah1, ah0)                                     \
+	}
+#define PF6_GROUP(HV, LV, gi)                                                  \
+	{                                                                          \
+		const uint32_t *qw = qd + (uint64_t)(gi) * PF6_QWORDS;                 \
+		PF6_DOT3((HV).x, 0, ah2, ah1, ah0)                                     \
+		PF6_DOT3((HV).y, 1, ah2, ah1, ah0)                                     \
+		PF6_DOT3((HV).z, 2, ah2, ah1, ah0)                                     \
+		PF6_DOT3((HV).w, 3, ah2, ah1, ah0)                                     \
+		PF6_DOT3((LV).x & 0x33333333u, 0, al2, al1, al0)                       \
+		PF6_DOT3(((LV).x >> 2) & 0x33333333u, 1, al2, al1, al0)                \
+		PF6_DOT3((LV).y & 0x33333333u, 2, al2, al1, al0)                       \
+		PF6_DOT3(((LV).y >> 2) & 0x33333333u, 3, al2, al1, al0)                \
+	}
+
+// The int6 tier's finish, shared by the stream and by k_pf4_refine: N from
+// the six digit sums, then a and e.
+#define PF6_N(xs, qb)                                                          \
+	((int32_t)(4u * (256u * ah2 + 16u * ah1 + ah0) + 256u * al2 + 16u * al1 +  \
+	           al0 - 2048u * (xs) + (qb)))
+#define PF6_A(N, ps, qscale)                                                   \
+	__fsub_rn(1.0f, __fmul_rn(__fmul_rn((float)(N), (ps)), (qscale)))
+#define PF6_E(pe, qeps)                                                        \
+	__fadd_rn((pe), __fmul_rn(__fadd_rn(1.0f, (pe)), (qeps)))
+
+template <bool MASKED, bool H4 = false>
 __global__ __launch_bounds__(THREADS) void k_prefilter_i6(
     const uint4 *__restrict__ hp, const uint2 *__restrict__ lp,
     const float *__restrict__ pscale, const float *__restrict__ peps,
@@ -1476,7 +1580,11 @@ __global__ __launch_bounds__(THREADS) void k_prefilter_i6(
 	__shared__ int topk_n;
 	__shared__ uint64_t kth;
 
+	static_assert(!(MASKED && H4), "the H-only stream has no masked variant");
 	pf_topk_init(cnt, topk_n, kth, cand_cnt);
+	if constexpr (H4)
+		if (blockIdx.x == 0 && threadIdx.x == 0)
+			cand_cnt[1] = 0;
 
 	uint64_t row_begin = (uint64_t)blockIdx.x * rows_per_block;
 	uint64_t row_end = row_begin + rows_per_block;
@@ -1503,23 +1611,23 @@ __global__ __launch_bounds__(THREADS) void k_prefilter_i6(
 				allowed = (mw >> (r & 63)) & 1ULL;
 				live = __ballot(mw != 0ULL) != 0ULL;
 			}
-#define PF6_DOT3(X, m, a2, a1, a0)                                             \
-	a2 = __builtin_amdgcn_udot8((X), qw[0 + (m)], a2, false);                  \
-	a1 = __builtin_amdgcn_udot8((X), qw[4 + (m)], a1, false);                  \
-	a0 = __builtin_amdgcn_udot8((X), qw[8 + (m)], a0, false);
-#define PF6_GROUP(HV, LV, gi)                                                  \
-	{                                                                          \
-		const uint32_t *qw = qd + (uint64_t)(gi) * PF6_QWORDS;                 \
-		PF6_DOT3((HV).x, 0, ah2, ah1, ah0)                                     \
-		PF6_DOT3((HV).y, 1, ah2, ah1, ah0)                                     \
-		PF6_DOT3((HV).z, 2, ah2, ah1, ah0)                                     \
-		PF6_DOT3((HV).w, 3, ah2, ah1, ah0)                                     \
-		PF6_DOT3((LV).x & 0x33333333u, 0, al2, al1, al0)                       \
-		PF6_DOT3(((LV).x >> 2) & 0x33333333u, 1, al2, al1, al0)                \
-		PF6_DOT3((LV).y & 0x33333333u, 2, al2, al1, al0)                       \
-		PF6_DOT3(((LV).y >> 2) & 0x33333333u, 3, al2, al1, al0)                \
-	}
-			if (live) {
+			if constexpr (H4) {
+				uint32_t g = 0;
+				for (; g + PF4_UNROLL <= ngroups; g += PF4_UNROLL) {
+					pf6_v4 hv[PF4_UNROLL];
+#pragma unroll
+					for (uint32_t j = 0; j < PF4_UNROLL; j++)
+						hv[j] = __builtin_nontemporal_load(
+						    (const pf6_v4 *)(ph + (uint64_t)(g + j) * sn_pad));
+#pragma unroll
+					for (uint32_t j = 0; j < PF4_UNROLL; j++)
+						PF6_GROUP_H(hv[j], g + j)
+				}
+				for (; g < ngroups; g++) {
+					const uint4 hv1 = ph[(uint64_t)g * sn_pad];
+					PF6_GROUP_H(hv1, g)
+				}
+			} else if (live) {
 				uint32_t g = 0;
 				for (; g + PF6_UNROLL <= ngroups; g += PF6_UNROLL) {
 					pf6_v4 hv[PF6_UNROLL];
@@ -1541,16 +1649,14 @@ __global__ __launch_bounds__(THREADS) void k_prefilter_i6(
 					PF6_GROUP(hv1, lv1, g)
 				}
 			}
-#undef PF6_GROUP
-#undef PF6_DOT3
-			const uint32_t S = 4u * (256u * ah2 + 16u * ah1 + ah0) +
-			                   256u * al2 + 16u * al1 + al0;
-			const int32_t N = (int32_t)(S - 2048u * xsum[r] + qbias);
+			const int32_t N =
+			    H4 ? (int32_t)(8u * (256u * ah2 + 16u * ah1 + ah0) -
+			                   16384u * xsum[r] + qbias)
+			       : PF6_N(xsum[r], qbias);
 			const float pe = peps[r];
-			const float a = __fsub_rn(
-			    1.0f, __fmul_rn(__fmul_rn((float)N, pscale[r]), qscale));
-			const float e =
-			    __fadd_rn(pe, __fmul_rn(__fadd_rn(1.0f, pe), qeps));
+			const float a = PF6_A(
+			    N, H4 ? __fmul_rn(pscale[r], 0.5f) : pscale[r], qscale);
+			const float e = PF6_E(pe, qeps);
 			const bool ok = allowed && r < row_end &&
 			                (__float_as_uint(a) & 0x7F800000u) != 0x7F800000u;
 			if constexpr (MASKED)
@@ -1609,7 +1715,64 @@ __global__ void k_pf_compact(const float *__restrict__ scores, uint64_t n,
 // partial sums, the same combine, the same tail, the f64 finish with
 // norms[r]. Euclidean runs the sequential chain of k_scan<1, .> /
 // k_gather_dist<1> on lane 0. qs, xs ([MAX_D]) and ps ([8]) are the calling
-// kernel's LDS.
+// kernel's LDS. rows_exact_one is one row of it, *out = Cand{dist, ids[r]},
+// with the query already in qs (the barrier it opens with orders that).
+template <int METRIC>
+__device__ __forceinline__ static void rows_exact_one(
+    const float *__restrict__ cm, const double *__restrict__ norms,
+    const uint64_t *__restrict__ ids, uint64_t n_pad, uint32_t d,
+    double q_norm, uint32_t r, Cand *__restrict__ out, float *qs, float *xs,
+    float *ps) {
+	__syncthreads();
+	for (uint32_t i = threadIdx.x; i < d; i += 64)
+		xs[i] = cm[(uint64_t)i * n_pad + r];
+	__syncthreads();
+	if (METRIC == 0) {
+		// the chain's 8 partial sums are independent of each other: lane
+		// j runs partial j's own sequence, lane 0 then combines them in
+		// the chain's order — the same operations on the same values
+		const uint32_t d8 = d & ~7u;
+		if (threadIdx.x < 8) {
+			float pj = 0.f;
+			for (uint32_t i = threadIdx.x; i < d8; i += 8)
+				pj = __fadd_rn(pj, __fmul_rn(xs[i], qs[i]));
+			ps[threadIdx.x] = pj;
+		}
+		__syncthreads();
+		if (threadIdx.x == 0) {
+			float p[8];
+#pragma unroll
+			for (int j = 0; j < 8; j++)
+				p[j] = ps[j];
+			uint32_t k8 = d8;
+			float sum = 0.f;
+			sum = __fadd_rn(sum, __fadd_rn(p[0], p[4]));
+			sum = __fadd_rn(sum, __fadd_rn(p[1], p[5]));
+			sum = __fadd_rn(sum, __fadd_rn(p[2], p[6]));
+			sum = __fadd_rn(sum, __fadd_rn(p[3], p[7]));
+			for (; k8 < d; k8++)
+				sum = __fadd_rn(sum, __fmul_rn(xs[k8], qs[k8]));
+			double den = q_norm * norms[r];
+			Cand o;
+			o.dist = 1.0 - (double)sum / den;
+			o.id = ids[r];
+			*out = o;
+		}
+	} else {
+		if (threadIdx.x == 0) {
+			float acc = 0.f;
+			for (uint32_t kk = 0; kk < d; kk++) {
+				float diff = xs[kk] - qs[kk];
+				acc = __fadd_rn(acc, __fmul_rn(diff, diff));
+			}
+			Cand o;
+			o.dist = sqrt((double)acc);
+			o.id = ids[r];
+			*out = o;
+		}
+	}
+}
+
 template <int METRIC>
 __device__ __forceinline__ static void rows_exact(
     const float *__restrict__ cm, const double *__restrict__ norms,
@@ -1619,57 +1782,9 @@ __device__ __forceinline__ static void rows_exact(
     float *qs, float *xs, float *ps) {
 	for (uint32_t i = threadIdx.x; i < d; i += 64)
 		qs[i] = qg[i];
-	for (uint32_t c = blockIdx.x; c < cnt; c += gridDim.x) {
-		__syncthreads();
-		const uint32_t r = rows[c];
-		for (uint32_t i = threadIdx.x; i < d; i += 64)
-			xs[i] = cm[(uint64_t)i * n_pad + r];
-		__syncthreads();
-		if (METRIC == 0) {
-			// the chain's 8 partial sums are independent of each other: lane
-			// j runs partial j's own sequence, lane 0 then combines them in
-			// the chain's order — the same operations on the same values
-			const uint32_t d8 = d & ~7u;
-			if (threadIdx.x < 8) {
-				float pj = 0.f;
-				for (uint32_t i = threadIdx.x; i < d8; i += 8)
-					pj = __fadd_rn(pj, __fmul_rn(xs[i], qs[i]));
-				ps[threadIdx.x] = pj;
-			}
-			__syncthreads();
-			if (threadIdx.x == 0) {
-				float p[8];
-#pragma unroll
-				for (int j = 0; j < 8; j++)
-					p[j] = ps[j];
-				uint32_t k8 = d8;
-				float sum = 0.f;
-				sum = __fadd_rn(sum, __fadd_rn(p[0], p[4]));
-				sum = __fadd_rn(sum, __fadd_rn(p[1], p[5]));
-				sum = __fadd_rn(sum, __fadd_rn(p[2], p[6]));
-				sum = __fadd_rn(sum, __fadd_rn(p[3], p[7]));
-				for (; k8 < d; k8++)
-					sum = __fadd_rn(sum, __fmul_rn(xs[k8], qs[k8]));
-				double den = q_norm * norms[r];
-				Cand o;
-				o.dist = 1.0 - (double)sum / den;
-				o.id = ids[r];
-				out[c] = o;
-			}
-		} else {
-			if (threadIdx.x == 0) {
-				float acc = 0.f;
-				for (uint32_t kk = 0; kk < d; kk++) {
-					float diff = xs[kk] - qs[kk];
-					acc = __fadd_rn(acc, __fmul_rn(diff, diff));
-				}
-				Cand o;
-				o.dist = sqrt((double)acc);
-				o.id = ids[r];
-				out[c] = o;
-			}
-		}
-	}
+	for (uint32_t c = blockIdx.x; c < cnt; c += gridDim.x)
+		rows_exact_one<METRIC>(cm, norms, ids, n_pad, d, q_norm, rows[c],
+		                       out + c, qs, xs, ps);
 }
 
 // Exact rescore of the prefilter's candidates: rows_exact<0> over the count
@@ -1721,6 +1836,189 @@ __global__ __launch_bounds__(THREADS) void k_pf_final(
 	}
 	merge_slice(cands, total, k, total, out);
 }
+
+// ---------------------------------------------------------------------------
+// Two-stage int6 path: k_prefilter_i6<false, true> streams
+// plane H alone; the kernels here turn its scores into the candidate list
+// that k_pf_rescore and k_pf_final take as from k_pf_compact.
+// ---------------------------------------------------------------------------
+#define PF4_LIST_CAP 262144u /* first list: 1 MB of rows */
+#define PF4_BLOCK_LIST 8192  /* rows a block collects before it reserves */
+#define PF4_PASSES 4         /* score loads a lane has in flight */
+#ifndef PF4_REFINE_LANES
+#define PF4_REFINE_LANES 32 /* lanes that share one listed row */
+#endif
+
+// Exact distances of the K rows with the smallest H-only upper bounds
+// (approx_top of launch_merge_tree: id = row position), one 64-lane
+// workgroup each: out[c] = rows_exact<0> of row approx_top[c].id, or +inf
+// for an entry without a row (fewer than K rows carry a bound).
+__global__ __launch_bounds__(64) void k_pf4_threshold(
+    const float *__restrict__ cm, const double *__restrict__ norms,
+    const uint64_t *__restrict__ ids, uint64_t n_pad, uint32_t d,
+    const float *__restrict__ qg, double q_norm,
+    const Cand *__restrict__ approx_top, Cand *__restrict__ out) {
+	__shared__ float qs[MAX_D];
+	__shared__ float xs[MAX_D];
+	__shared__ float ps[8];
+	const uint64_t r = approx_top[blockIdx.x].id;
+	if (r == ~0ULL) { // uniform
+		if (threadIdx.x == 0) {
+			Cand o;
+			o.dist = __longlong_as_double(0x7FF0000000000000LL);
+			o.id = ~0ULL;
+			out[blockIdx.x] = o;
+		}
+		return;
+	}
+	for (uint32_t i = threadIdx.x; i < d; i += 64)
+		qs[i] = qg[i];
+	rows_exact_one<0>(cm, norms, ids, n_pad, d, q_norm, (uint32_t)r,
+	                  out + blockIdx.x, qs, xs, ps);
+}
+
+// T = the largest of the k threshold distances in total_cmp order, for every
+// thread of the block (k <= MAX_K <= blockDim.x; key is the caller's LDS).
+// The exact distances of K distinct rows bound the true Kth distance from
+// above, so a row whose lower bound exceeds T is in no top-K, ties included.
+__device__ __forceinline__ static double pf4_threshold(
+    const Cand *__restrict__ thr, uint32_t k, unsigned long long *key) {
+	if (threadIdx.x == 0)
+		*key = 0;
+	__syncthreads();
+	if (threadIdx.x < k)
+		atomicMax(key, (unsigned long long)d_total_key(thr[threadIdx.x].dist));
+	__syncthreads();
+	const uint64_t kb = *key;
+	return __longlong_as_double(
+	    (long long)((kb >> 63) ? (kb & 0x7FFFFFFFFFFFFFFFULL) : ~kb));
+}
+
+// k_pf_compact against T, for a list of thousands of rows: a block collects
+// the rows of its whole grid-stride loop in LDS and reserves list space with
+// one global atomic per PF4_BLOCK_LIST rows at most (the list's order is
+// arbitrary as before); a lane loads PF4_PASSES score quads before the block
+// meets at a barrier, so the loads of a round overlap. A row passes unless
+// its score is above T: -inf, the rows without a bound, always does. The
+// counter keeps counting past list_cap <= PF4_LIST_CAP; the list is never
+// written past it.
+__global__ __launch_bounds__(THREADS) void k_pf4_compact(
+    const float *__restrict__ scores, uint64_t n,
+    const Cand *__restrict__ thr, uint32_t k, uint32_t list_cap,
+    uint32_t *__restrict__ list_cnt, uint32_t *__restrict__ list_rows) {
+	__shared__ uint32_t rows[PF4_BLOCK_LIST];
+	__shared__ uint32_t cnt, base;
+	__shared__ unsigned long long tkey;
+	if (threadIdx.x == 0)
+		cnt = 0;
+	const double T = pf4_threshold(thr, k, &tkey);
+	const uint64_t ngrp = (n + 3) / 4;
+	const uint64_t round = (uint64_t)THREADS * PF4_PASSES;
+	// g0 is uniform, so every thread of the block meets every barrier
+	for (uint64_t g0 = (uint64_t)blockIdx.x * round;;
+	     g0 += (uint64_t)gridDim.x * round) {
+		const bool last = g0 >= ngrp;
+		float4 s[PF4_PASSES];
+#pragma unroll
+		for (int p = 0; p < PF4_PASSES; p++) {
+			const uint64_t g = g0 + (uint64_t)p * THREADS + threadIdx.x;
+			if (g < ngrp)
+				s[p] = *(const float4 *)(scores + g * 4);
+		}
+#pragma unroll
+		for (int p = 0; p < PF4_PASSES; p++) {
+			const uint64_t g = g0 + (uint64_t)p * THREADS + threadIdx.x;
+			if (g >= ngrp)
+				continue;
+			const float v[4] = {s[p].x, s[p].y, s[p].z, s[p].w};
+#pragma unroll
+			for (int c = 0; c < 4; c++) {
+				const uint64_t r = g * 4 + c;
+				if (r < n && !((double)v[c] > T))
+					rows[atomicAdd(&cnt, 1u)] = (uint32_t)r;
+			}
+		}
+		__syncthreads();
+		const uint32_t m = cnt;
+		__syncthreads();
+		// one round adds at most 4 * round rows: flush while that still fits
+		if (m > PF4_BLOCK_LIST - 4 * THREADS * PF4_PASSES || (last && m > 0)) {
+			if (threadIdx.x == 0) {
+				base = atomicAdd(list_cnt, m);
+				cnt = 0;
+			}
+			__syncthreads();
+			for (uint32_t i = threadIdx.x; i < m; i += THREADS)
+				if (base + i < list_cap)
+					list_rows[base + i] = rows[i];
+			__syncthreads();
+		}
+		if (last)
+			break;
+	}
+}
+
+// The second test: PF4_REFINE_LANES lanes gather one listed row's H and L
+// words, group by group, and add up the six digit sums (exact integers, any
+// order); the row goes on to cand_rows (cap PF_CAND_CAP, as k_pf_compact
+// fills it) unless its int6 lower bound, k_prefilter_i6's own a - e, is
+// above T, and always if it carries no bound. An overflowed first list is
+// left alone: the host then runs the plain int6 path.
+__global__ __launch_bounds__(THREADS) void k_pf4_refine(
+    const uint4 *__restrict__ hp, const uint2 *__restrict__ lp,
+    const float *__restrict__ pscale, const float *__restrict__ peps,
+    const uint32_t *__restrict__ xsum, uint64_t sn_pad, uint32_t ngroups,
+    const uint32_t *__restrict__ qd, float qscale, float qeps, uint32_t qbias,
+    const Cand *__restrict__ thr, uint32_t k, uint32_t list_cap,
+    const uint32_t *__restrict__ list_cnt,
+    const uint32_t *__restrict__ list_rows, uint32_t *__restrict__ cand_cnt,
+    uint32_t *__restrict__ cand_rows) {
+	__shared__ unsigned long long tkey;
+	const double T = pf4_threshold(thr, k, &tkey);
+	const uint32_t m = *list_cnt;
+	if (m > list_cap)
+		return;
+	const uint32_t sub = threadIdx.x % PF4_REFINE_LANES;
+	const uint32_t per_grid = gridDim.x * (THREADS / PF4_REFINE_LANES);
+	for (uint32_t c = (blockIdx.x * THREADS + threadIdx.x) / PF4_REFINE_LANES;
+	     c < m; c += per_grid) { // uniform over the lanes of one row
+		const uint32_t r = list_rows[c];
+		uint32_t ah2 = 0, ah1 = 0, ah0 = 0, al2 = 0, al1 = 0, al0 = 0;
+		for (uint32_t g = sub; g < ngroups; g += PF4_REFINE_LANES) {
+			const uint4 hv = hp[(uint64_t)g * sn_pad + r];
+			const uint2 lv = lp[(uint64_t)g * sn_pad + r];
+			PF6_GROUP(hv, lv, g)
+		}
+#pragma unroll
+		for (int off = PF4_REFINE_LANES / 2; off > 0; off >>= 1) {
+			ah2 += __shfl_xor(ah2, off);
+			ah1 += __shfl_xor(ah1, off);
+			ah0 += __shfl_xor(ah0, off);
+			al2 += __shfl_xor(al2, off);
+			al1 += __shfl_xor(al1, off);
+			al0 += __shfl_xor(al0, off);
+		}
+		if (sub == 0) {
+			const int32_t N = PF6_N(xsum[r], qbias);
+			const float pe = peps[r];
+			const float a = PF6_A(N, pscale[r], qscale);
+			const float e = PF6_E(pe, qeps);
+			const bool covered =
+			    (__float_as_uint(a) & 0x7F800000u) != 0x7F800000u;
+			if (!covered || !((double)__fsub_rn(a, e) > T)) {
+				const uint32_t idx = atomicAdd(cand_cnt, 1u);
+				if (idx < PF_CAND_CAP)
+					cand_rows[idx] = r;
+			}
+		}
+	}
+}
+#undef PF6_E
+#undef PF6_A
+#undef PF6_N
+#undef PF6_GROUP
+#undef PF6_GROUP_H
+#undef PF6_DOT3
 
 // All-distance kernel: one lane per row, feature-major coalesced reads.
 // Used for parity dumps, k > MAX_K, and (as the product path proper) the
@@ -3027,7 +3325,8 @@ void sdbv_shutdown(sdbv_ctx *ctx) {
 	if (ctx->q_dev)
 		(void)hipFree(ctx->q_dev);
 	for (void *p : {(void *)ctx->pf_scores, (void *)ctx->pf_rows,
-	                ctx->pf_cands, ctx->pf_res})
+	                ctx->pf_cands, ctx->pf_res, (void *)ctx->pf4_list,
+	                ctx->pf4_thr})
 		if (p)
 			(void)hipFree(p);
 	for (void *p : {(void *)ctx->S, ctx->bstate, (void *)ctx->Q_dev,
@@ -3115,13 +3414,16 @@ static void free_shadow(sdbv_ctx *ctx, Table *t) {
 
 // What the three shadow tiers differ in, by Shadow::kind: the rows of one
 // block-sweep of the tier's prefilter kernel (sn_pad is a multiple of it),
-// the f32-sized side values per row, and (below) the code bytes.
+// the f32-sized side values per row, and (below) the code bytes. Entry 4 is
+// the int6 tier's H-only stream, for prefilter_grid alone: its spans are
+// whole sweeps of THREADS rows, not whole tiles, which left a fifth of the
+// device's 8 blocks per CU empty at 10M rows (profiles/prefilter_h4.md).
 struct ShadowTier {
 	uint64_t tile;
 	uint64_t side_per_row;
 };
-static const ShadowTier SHADOW_TIERS[4] = {
-    {0, 0}, {PF_TILE, 1}, {PF8_TILE, 2}, {PF6_TILE, 3}};
+static const ShadowTier SHADOW_TIERS[5] = {
+    {0, 0}, {PF_TILE, 1}, {PF8_TILE, 2}, {PF6_TILE, 3}, {THREADS, 0}};
 
 // bf16: 2 d bytes per row (+50 % of the f32 store); int8: d (+25 %); int6:
 // 0.75 d_pad, d_pad = d rounded up to a multiple of 32 (planes H and L).
@@ -3136,20 +3438,26 @@ static uint64_t shadow_code_bytes(int kind, uint32_t d, uint64_t sn_pad) {
 // Build the kind shadow of a staged cosine table (norms already computed, in
 // stream order), instead of any other kind the table holds. A failed
 // allocation leaves the table without a shadow and returns SDBV_ERR_OOM.
-static int build_shadow(sdbv_ctx *ctx, Table *t, int kind) {
+// h4 (int6 only): with the H-only side data, 8 B per row more. Staging asks
+// for it when h4_policy holds; the explicit entries build the plain shadow,
+// also in place of a staged one that carries the side data.
+static int build_shadow(sdbv_ctx *ctx, Table *t, int kind, bool h4 = false) {
 	if (t->metric != SDBV_METRIC_COSINE)
 		return SDBV_ERR_UNSUPPORTED;
-	if (t->sh.kind == kind)
+	h4 = h4 && kind == 3;
+	if (t->sh.kind == kind && t->sh.h4 == h4)
 		return SDBV_OK;
 	if (t->sh.kind)
 		free_shadow(ctx, t);
 	const ShadowTier &tier = SHADOW_TIERS[kind];
 	Shadow sh;
+	sh.h4 = h4;
 	sh.sn_pad = ((t->n + tier.tile - 1) / tier.tile) * tier.tile;
 	if (sh.sn_pad == 0)
 		sh.sn_pad = tier.tile;
 	const uint64_t code_bytes = shadow_code_bytes(kind, t->d, sh.sn_pad);
-	const uint64_t side_bytes = tier.side_per_row * sh.sn_pad * sizeof(float);
+	const uint64_t side_bytes =
+	    (tier.side_per_row + (sh.h4 ? 2 : 0)) * sh.sn_pad * sizeof(float);
 	if (hipMalloc(&sh.codes, code_bytes) != hipSuccess ||
 	    hipMalloc(&sh.side, side_bytes) != hipSuccess) {
 		(void)hipGetLastError(); // allocation failure is not sticky
@@ -3181,7 +3489,8 @@ static int build_shadow(sdbv_ctx *ctx, Table *t, int kind) {
 		hipLaunchKernelGGL(k_shadow_i6, dim3((uint32_t)(sn_pad / 256)),
 		                   dim3(256), 0, ctx->stream, t->cm, t->norms,
 		                   sh.plane_h(), sh.plane_l(t->d), sh.pscale(),
-		                   sh.peps(), sh.xsum(), t->n, t->n_pad, sn_pad, t->d);
+		                   sh.peps(), sh.xsum(), sh.peps4(), sh.xsum_h(), t->n,
+		                   t->n_pad, sn_pad, t->d);
 		break;
 	}
 	HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
@@ -3198,6 +3507,10 @@ static int build_shadow(sdbv_ctx *ctx, Table *t, int kind) {
 #define PF_DEFAULT_MIN_ROWS 500000ull
 #define PF8_DEFAULT_MIN_ROWS 500000ull
 #define PF6_DEFAULT_MIN_ROWS 500000ull
+// The two-stage int6 path rather than the plain one: a tie at 500 000 rows,
+// ahead from 1 000 000 (profiles/prefilter_h4.md); never below
+// PF6_DEFAULT_MIN_ROWS.
+#define PF4_DEFAULT_MIN_ROWS 1000000ull
 
 // One staging policy question: env_flag=0 answers no; otherwise the table
 // needs env_min_rows rows (default default_min). The three row counts are
@@ -3212,6 +3525,15 @@ static bool shadow_policy(const Table *t, const char *env_flag,
 	if (m && *m)
 		min_rows = strtoull(m, nullptr, 10);
 	return t->n >= min_rows;
+}
+
+// The two-stage path's question, asked when staging builds an int6 shadow
+// (for its side data) and again at every call: SDBV_SCAN_PREFILTER_H4 and
+// SDBV_SCAN_PREFILTER_H4_MIN_ROWS.
+static bool h4_policy(const Table *t) {
+	return shadow_policy(t, "SDBV_SCAN_PREFILTER_H4",
+	                     "SDBV_SCAN_PREFILTER_H4_MIN_ROWS",
+	                     PF4_DEFAULT_MIN_ROWS);
 }
 
 // The shadow that scan staging builds: none off cosine or when
@@ -3253,7 +3575,7 @@ static int finish_stage(sdbv_ctx *ctx, Table *t, bool scan_table) {
 	// asks for one; without the memory for it the table simply has none
 	const int kind = scan_table ? staged_shadow_kind(t) : 0;
 	if (kind) {
-		int rc = build_shadow(ctx, t, kind);
+		int rc = build_shadow(ctx, t, kind, kind == 3 && h4_policy(t));
 		if (rc != SDBV_OK && rc != SDBV_ERR_OOM)
 			return rc;
 	}
@@ -3370,6 +3692,22 @@ int sdbv_prefilter_i6_row(const float *x, uint32_t d, double norm,
 		    (l[g * 2 + (i >> 4)] >> (2 * (f < 8 ? 2 * f : 2 * (f - 8) + 1))) &
 		    3u;
 		codes[k] = (int8_t)((int)(hi * 4 + lo) - 32);
+	}
+	return SDBV_OK;
+}
+
+int sdbv_prefilter_h4_row(const float *x, uint32_t d, double norm,
+                          uint8_t *codes_h, float *scale, float *eps4,
+                          uint32_t *xsum_h) {
+	if (!x || !codes_h || !scale || !eps4 || !xsum_h || d == 0 || d > MAX_D)
+		return SDBV_ERR_BAD_ARG;
+	uint32_t h[MAX_D / 32 * 4], l[MAX_D / 32 * 2], xsum;
+	float pscale, eps;
+	pf_i6_row(x, 1, d, norm, h, 4, l, 2, scale, &pscale, &eps, &xsum, eps4,
+	          xsum_h);
+	for (uint32_t k = 0; k < d; k++) {
+		const uint32_t g = k / 32, i = k % 32;
+		codes_h[k] = (uint8_t)((h[g * 4 + (i >> 3)] >> (4 * (i & 7))) & 15u);
 	}
 	return SDBV_OK;
 }
@@ -3652,7 +3990,8 @@ static int knn_large_k(sdbv_ctx *ctx, Table &t, const float *q, uint32_t d,
 	return SDBV_OK;
 }
 
-// Row-span grid of the prefilter sweep of shadow tier kind (1..3): contiguous
+// Row-span grid of the prefilter sweep of shadow tier kind (1..3; 4 = the
+// int6 tier's H-only stream, unmasked only): contiguous
 // spans of the tier's tiles, sized so that the whole grid is resident at once
 // (one round, every block the same span). A grid of a few more blocks than
 // the chip holds runs a second, mostly empty round with too few bytes in
@@ -3676,6 +4015,9 @@ static uint64_t prefilter_grid(sdbv_ctx *ctx, uint64_t n, int kind,
 		case 3:
 			kernel = masked ? (const void *)k_prefilter_i6<true>
 			                : (const void *)k_prefilter_i6<false>;
+			break;
+		case 4:
+			kernel = (const void *)k_prefilter_i6<false, true>;
 			break;
 		}
 		hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(
@@ -3704,6 +4046,7 @@ struct PfQ6 { // int6 tier: the quantised query's kernel operands
 	float qscale = 0.f; // f32(sq / |q|)
 	float qeps = 0.f;   // 1.01 rho_q, rounded up
 	uint32_t bias = 0;  // 65536 d_pad - 32 sum qu (mod 2^32)
+	uint32_t bias4 = 0; // the H-only stream's: -61 sum cq (mod 2^32)
 };
 
 static inline int shadow_kind(const Table &t) { return t.sh.kind; }
@@ -3726,6 +4069,7 @@ static int stage_query_pf(sdbv_ctx *ctx, const float *q, uint32_t d,
 		q6->qscale = (float)((double)sq / q_norm);
 		q6->qeps = rho > 0.f ? pf_round_up_f32(1.01 * (double)rho) : 0.f;
 		q6->bias = 65536u * (32u * G) - 32u * qs;
+		q6->bias4 = 61u * (2048u * (32u * G) - qs);
 	} else if (kind == 2) {
 		double qsum = 0.0;
 		for (uint32_t i = 0; i < d; i++)
@@ -3733,6 +4077,27 @@ static int stage_query_pf(sdbv_ctx *ctx, const float *q, uint32_t d,
 		*qbias = (float)(128.0 * qsum);
 	}
 	return stage_query(ctx, q, d, q_bytes);
+}
+
+// Device scratch of both prefilter paths: scores for sn_pad rows, the
+// candidate list, its rescored Cands and the result block with the counters.
+static int ensure_prefilter_scratch(sdbv_ctx *ctx, uint64_t sn_pad) {
+	if (ctx->pf_scores_cap < sn_pad) {
+		if (ctx->pf_scores)
+			(void)hipFree(ctx->pf_scores);
+		ctx->pf_scores = nullptr;
+		ctx->pf_scores_cap = 0;
+		HIP_CHECK(ctx, hipMalloc(&ctx->pf_scores, sn_pad * sizeof(float)));
+		ctx->pf_scores_cap = sn_pad;
+	}
+	if (!ctx->pf_rows)
+		HIP_CHECK(ctx, hipMalloc(&ctx->pf_rows,
+		                         PF_CAND_CAP * sizeof(uint32_t)));
+	if (!ctx->pf_cands)
+		HIP_CHECK(ctx, hipMalloc(&ctx->pf_cands, PF_CAND_CAP * sizeof(Cand)));
+	if (!ctx->pf_res)
+		HIP_CHECK(ctx, hipMalloc(&ctx->pf_res, (MAX_K + 2) * sizeof(Cand)));
+	return SDBV_OK;
 }
 
 // The prefilter path of sdbv_knn_bruteforce (cosine, k <= MAX_K, table with
@@ -3750,21 +4115,9 @@ static int knn_prefilter(sdbv_ctx *ctx, Table &t, uint32_t k, double q_norm,
                          Cand *host_out, uint32_t *ncand) {
 	const Shadow &sh = t.sh;
 	const int kind = sh.kind;
-	if (ctx->pf_scores_cap < sh.sn_pad) {
-		if (ctx->pf_scores)
-			(void)hipFree(ctx->pf_scores);
-		ctx->pf_scores = nullptr;
-		ctx->pf_scores_cap = 0;
-		HIP_CHECK(ctx, hipMalloc(&ctx->pf_scores, sh.sn_pad * sizeof(float)));
-		ctx->pf_scores_cap = sh.sn_pad;
-	}
-	if (!ctx->pf_rows)
-		HIP_CHECK(ctx, hipMalloc(&ctx->pf_rows,
-		                         PF_CAND_CAP * sizeof(uint32_t)));
-	if (!ctx->pf_cands)
-		HIP_CHECK(ctx, hipMalloc(&ctx->pf_cands, PF_CAND_CAP * sizeof(Cand)));
-	if (!ctx->pf_res)
-		HIP_CHECK(ctx, hipMalloc(&ctx->pf_res, (MAX_K + 2) * sizeof(Cand)));
+	int rc = ensure_prefilter_scratch(ctx, sh.sn_pad);
+	if (rc != SDBV_OK)
+		return rc;
 
 	uint64_t rows_per_block = 0;
 	uint64_t nblocks =
@@ -3852,6 +4205,115 @@ static int knn_prefilter(sdbv_ctx *ctx, Table &t, uint32_t k, double q_norm,
 	return SDBV_OK;
 }
 
+// SDBV_SCAN_PREFILTER_H4_LIST_MAX, read at each call: the capacity of the
+// two-stage path's first list. Default and ceiling PF4_LIST_CAP.
+static uint32_t pf4_list_max() {
+	uint64_t cap = PF4_LIST_CAP;
+	const char *e = getenv("SDBV_SCAN_PREFILTER_H4_LIST_MAX");
+	if (e && *e) {
+		uint64_t v = strtoull(e, nullptr, 10);
+		if (v < cap)
+			cap = v;
+	}
+	return (uint32_t)cap;
+}
+
+// The two-stage path of sdbv_knn_bruteforce over an int6 shadow with the
+// H-only side data (conditions and outputs as for knn_prefilter, unmasked;
+// DESIGN.md §11d): stream plane H alone, take T from the exact distances of
+// the K rows with the smallest H-only upper bounds, list the rows whose
+// H-only lower bound is not above T, keep of those the rows whose int6 lower
+// bound is not above T, then rescore and select as knn_prefilter does.
+// *nstage1 receives the first list's raw count; above list_cap that list
+// overflowed, nothing behind it ran and host_out is void: the caller takes
+// knn_prefilter. host_out needs MAX_K + 2 entries: the one D2H copy carries
+// the device counters behind the results.
+static int knn_prefilter_h4(sdbv_ctx *ctx, Table &t, uint32_t k, double q_norm,
+                            const PfQ6 &q6, uint32_t list_cap, Cand *host_out,
+                            uint32_t *ncand, uint32_t *nstage1) {
+	const Shadow &sh = t.sh;
+	int rc = ensure_prefilter_scratch(ctx, sh.sn_pad);
+	if (rc != SDBV_OK)
+		return rc;
+	if (!ctx->pf4_list)
+		HIP_CHECK(ctx, hipMalloc(&ctx->pf4_list,
+		                         PF4_LIST_CAP * sizeof(uint32_t)));
+	if (!ctx->pf4_thr)
+		HIP_CHECK(ctx, hipMalloc(&ctx->pf4_thr, MAX_K * sizeof(Cand)));
+
+	uint64_t rows_per_block = 0;
+	const uint64_t nblocks =
+	    prefilter_grid(ctx, t.n, 4, false, &rows_per_block);
+	Cand *res = (Cand *)ctx->pf_res;
+	// device counters behind the results: [0] the candidates, [1] the first
+	// list
+	uint32_t *cand_cnt = (uint32_t *)&res[MAX_K + 1];
+	const uint32_t ngroups = (t.d + 31) / 32;
+	const uint32_t *qd = (const uint32_t *)(ctx->q_dev + t.d);
+	const Cand *thr = (const Cand *)ctx->pf4_thr;
+
+	HIP_CHECK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+	hipLaunchKernelGGL((k_prefilter_i6<false, true>), dim3((uint32_t)nblocks),
+	                   dim3(THREADS), 0, ctx->stream,
+	                   (const uint4 *)sh.plane_h(), (const uint2 *)nullptr,
+	                   sh.pscale(), sh.peps4(), sh.xsum_h(), t.n, sh.sn_pad,
+	                   ngroups, qd, q6.qscale, q6.qeps, q6.bias4, k,
+	                   rows_per_block, ctx->pf_scores, (Cand *)ctx->block_out,
+	                   cand_cnt, (const uint64_t *)nullptr);
+	HIP_CHECK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+	// K smallest H-only upper bounds -> final_out, id = row position
+	launch_merge_tree(ctx, nblocks, k);
+	HIP_CHECK(ctx, hipEventRecord(ctx->ev2, ctx->stream));
+	{
+		hipLaunchKernelGGL(k_pf4_threshold, dim3(k), dim3(64), 0, ctx->stream,
+		                   t.cm, t.norms, t.ids_dev, t.n_pad, t.d, ctx->q_dev,
+		                   q_norm, (const Cand *)ctx->final_out,
+		                   (Cand *)ctx->pf4_thr);
+		uint64_t ngrp = (t.n + 3) / 4;
+		uint64_t nb = (ngrp + THREADS * PF4_PASSES - 1) / (THREADS * PF4_PASSES);
+		if (nb > 512)
+			nb = 512;
+		if (nb == 0)
+			nb = 1;
+		hipLaunchKernelGGL(k_pf4_compact, dim3((uint32_t)nb), dim3(THREADS), 0,
+		                   ctx->stream, ctx->pf_scores, t.n, thr, k, list_cap,
+		                   cand_cnt + 1, ctx->pf4_list);
+		hipLaunchKernelGGL(k_pf4_refine, dim3(2048), dim3(THREADS), 0,
+		                   ctx->stream, (const uint4 *)sh.plane_h(),
+		                   (const uint2 *)sh.plane_l(t.d), sh.pscale(),
+		                   sh.peps(), sh.xsum(), sh.sn_pad, ngroups, qd,
+		                   q6.qscale, q6.qeps, q6.bias, thr, k, list_cap,
+		                   cand_cnt + 1, ctx->pf4_list, cand_cnt,
+		                   ctx->pf_rows);
+		hipLaunchKernelGGL(k_pf_rescore, dim3(PF_RESCORE_BLOCKS), dim3(64), 0,
+		                   ctx->stream, t.cm, t.norms, t.ids_dev, t.n_pad,
+		                   t.d, ctx->q_dev, q_norm, cand_cnt, ctx->pf_rows,
+		                   (Cand *)ctx->pf_cands);
+	}
+	HIP_CHECK(ctx, hipEventRecord(ctx->ev3, ctx->stream));
+	hipLaunchKernelGGL(k_pf_final, dim3(1), dim3(THREADS), 0, ctx->stream,
+	                   (Cand *)ctx->pf_cands, cand_cnt, k, res);
+	HIP_CHECK(ctx, hipEventRecord(ctx->ev4, ctx->stream));
+	HIP_CHECK(ctx, hipMemcpyAsync(host_out, res, (MAX_K + 2) * sizeof(Cand),
+	                              hipMemcpyDeviceToHost, ctx->stream));
+	HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+	HIP_CHECK(ctx, hipGetLastError());
+	*ncand = (uint32_t)host_out[k].id;
+	uint32_t counters[2];
+	std::memcpy(counters, &host_out[MAX_K + 1], sizeof(counters));
+	*nstage1 = counters[1];
+
+	float ms_pre = 0, ms_sel = 0, ms_rescore = 0, ms_final = 0;
+	(void)hipEventElapsedTime(&ms_pre, ctx->ev0, ctx->ev1);
+	(void)hipEventElapsedTime(&ms_sel, ctx->ev1, ctx->ev2);
+	(void)hipEventElapsedTime(&ms_rescore, ctx->ev2, ctx->ev3);
+	(void)hipEventElapsedTime(&ms_final, ctx->ev3, ctx->ev4);
+	ctx->stats.last_scan_kernel_ms = (double)ms_pre + ms_rescore;
+	ctx->stats.last_merge_kernel_ms = (double)ms_sel + ms_final;
+	ctx->stats.last_rows_scanned = t.n;
+	return SDBV_OK;
+}
+
 // The exact scan of sdbv_knn_bruteforce: k_scan over the f32 store, then the
 // tree merge; host_out[0..k) receives the top-k. q already in ctx->q_dev.
 // Caller holds ctx->mu.
@@ -3891,18 +4353,26 @@ int sdbv_knn_bruteforce(sdbv_ctx *ctx, uint64_t table, const float *q,
 		return SDBV_ERR_BAD_ARG;
 	ctx->stats.last_scan_path = 0;
 	ctx->stats.last_prefilter_candidates = 0;
+	ctx->stats.last_prefilter_stage1 = 0;
 	if (k > MAX_K || t.metric > SDBV_METRIC_EUCLIDEAN)
 		return knn_large_k(ctx, t, q, d, k, nullptr, out_ids, out_dists,
 		                   out_n);
 
 	uint64_t rows_per_block = 0;
 	const uint64_t nblocks = scan_grid(t.n, &rows_per_block);
-	// block_out serves whichever of the two grids runs
+	// block_out serves whichever of the grids runs
 	const int kind = shadow_kind(t);
+	// the two-stage path is chosen at each call, over an int6 shadow that
+	// was built with its side data
+	const bool use_h4 = kind == 3 && t.sh.h4 && h4_policy(&t);
 	uint64_t pf_rows_per_block = 0;
 	uint64_t scratch_blocks = std::max(
 	    nblocks,
 	    kind ? prefilter_grid(ctx, t.n, kind, false, &pf_rows_per_block) : 0);
+	if (use_h4)
+		scratch_blocks = std::max(
+		    scratch_blocks,
+		    prefilter_grid(ctx, t.n, 4, false, &pf_rows_per_block));
 	int rc = ensure_query_scratch(ctx, d, scratch_blocks, k);
 	if (rc != SDBV_OK)
 		return rc;
@@ -3920,8 +4390,23 @@ int sdbv_knn_bruteforce(sdbv_ctx *ctx, uint64_t table, const float *q,
 		return rc;
 
 	auto t_start = std::chrono::steady_clock::now();
-	Cand host_out[MAX_K + 1];
-	if (use_pf) {
+	Cand host_out[MAX_K + 2];
+	bool served = false; // by the two-stage path, overflowed or not
+	if (use_pf && use_h4) {
+		const uint32_t list_cap = pf4_list_max();
+		uint32_t ncand = 0, nstage1 = 0;
+		rc = knn_prefilter_h4(ctx, t, k, q_norm, q6, list_cap, host_out,
+		                      &ncand, &nstage1);
+		if (rc != SDBV_OK)
+			return rc;
+		ctx->stats.last_prefilter_stage1 = nstage1;
+		if (nstage1 <= list_cap) {
+			served = true;
+			ctx->stats.last_prefilter_candidates = ncand;
+			ctx->stats.last_scan_path = ncand <= PF_CAND_CAP ? 15u : 16u;
+		}
+	}
+	if (use_pf && !served) {
 		uint32_t ncand = 0;
 		rc = knn_prefilter(ctx, t, k, q_norm, qbias, q6, nullptr, host_out,
 		                   &ncand);
@@ -4118,6 +4603,7 @@ int sdbv_knn_bruteforce_filtered(sdbv_ctx *ctx, uint64_t table, const float *q,
 	                                        ctx->flt_rows_pin, list_max);
 	ctx->stats.last_scan_path = 0;
 	ctx->stats.last_prefilter_candidates = 0;
+	ctx->stats.last_prefilter_stage1 = 0;
 	ctx->stats.last_filter_rows = count;
 	ctx->stats.last_rows_scanned = count;
 	ctx->stats.last_scan_kernel_ms = 0;
