@@ -113,6 +113,16 @@ typedef struct sdbv_stats {
 	                                   list overflowed and the plain int6
 	                                   path served the call (path 5 / 6);
 	                                   0 on every other path */
+	uint64_t last_batch_exact_queries; /* queries of the last sdbv_knn_batch
+	                                      call that the single-query exact
+	                                      scan answered: norm outside
+	                                      [2^-30, 2^30], window certificate
+	                                      failed, or a table with more than
+	                                      1024 rows without a usable key */
+	uint32_t last_batch_refold; /* 1 if a candidate buffer of the fused kernel
+	                               overflowed in the last sdbv_knn_batch call
+	                               and all rows were selected again through
+	                               the rocBLAS pass, else 0 */
 } sdbv_stats;
 
 /* Create a context on HIP device `device` (-1 = current device). */
@@ -190,6 +200,16 @@ int sdbv_table_set_prefilter_i6(sdbv_ctx *, uint64_t table);
  * the shadow is built. */
 float sdbv_prefilter_eps(uint32_t d);
 float sdbv_bf16_rne(float x);
+/* Host-only: the proven bound on |key - E| that sdbv_knn_batch's window
+ * certificate uses, for a row and a query with norms in [2^-30, 2^30]
+ * (euclidean rows: at most 2^30). key is the row's f32 selection key,
+ * cosine -(s * f32(1 / norm)), euclidean sumsq - 2 s, with the f32 dot
+ * products s and sumsq summed in ANY order; E is the row's exact distance
+ * mapped into the key's domain in f64, cosine -(1 - dist) * q_norm, euclidean
+ * dist^2 - q_norm^2. metric 0 = cosine, 1 = euclidean; max_row_norm (euclidean
+ * only) is the largest staged row norm. */
+double sdbv_batch_key_bound(uint8_t metric, uint32_t d, double q_norm,
+                            double max_row_norm);
 /* Host-only: quantise one row of d <= 4096 f32 elements for the int8 shadow
  * exactly as staging does. norm = the row's staged norm (sqrt of the restated
  * f32 sum-of-squares chain, in f64). codes[k] = rint(x[k] / scale) in
@@ -327,7 +347,24 @@ uint64_t sdbv_filter_rows(const uint64_t *allow, uint64_t allow_words,
                           uint64_t n, uint32_t *out_rows, uint64_t cap);
 
 /* Batched-query brute-force: Q is b x d row-major; out_ids/out_dists are
- * b x k row-major. The dense Q x corpus^T product runs on MFMA. */
+ * b x k row-major, a query with fewer than k rows padded with id ~0 and
+ * distance +inf. The dense Q x corpus^T product runs on MFMA. Results (ids,
+ * order, distance bits) equal sdbv_knn_bruteforce's for every query.
+ *
+ * k is at most 48 on cosine and euclidean tables (SDBV_ERR_BAD_ARG above):
+ * per query the call selects a window of k + 16 <= 64 rows by an f32 key,
+ * recomputes those exactly, and then proves per query that the window holds
+ * the k nearest: the window's largest key must exceed the k-th exact distance
+ * mapped into the key's domain by more than sdbv_batch_key_bound. A query
+ * whose window fails that test (near-duplicate rows around the query), or
+ * whose norm is outside [2^-30, 2^30] (zero and non-finite included), is
+ * answered by the exact scan of sdbv_knn_bruteforce instead. Rows without a
+ * usable key (norm non-finite or above 2^30; on cosine tables also below
+ * 2^-30, zero included) never enter a window: staging lists them and every
+ * query gets their exact distances as well; a table with more than 1024 such
+ * rows is answered by the exact scan throughout.
+ * sdbv_stats.last_batch_exact_queries counts the queries the exact scan
+ * answered, last_batch_refold says whether a candidate buffer overflowed. */
 int sdbv_knn_batch(sdbv_ctx *, uint64_t table, const float *Q, uint32_t b,
                    uint32_t d, uint32_t k, uint64_t *out_ids,
                    double *out_dists);

@@ -56,6 +56,8 @@ class _Stats(ctypes.Structure):
         ("last_scan_path", ctypes.c_uint32),
         ("last_filter_rows", ctypes.c_uint64),
         ("last_prefilter_stage1", ctypes.c_uint64),
+        ("last_batch_exact_queries", ctypes.c_uint64),
+        ("last_batch_refold", ctypes.c_uint32),
     ]
 
 
@@ -106,6 +108,9 @@ def lib():
                                      f32p, ctypes.POINTER(ctypes.c_uint32)]
     L.sdbv_prefilter_eps.restype = ctypes.c_float
     L.sdbv_prefilter_eps.argtypes = [u32]
+    L.sdbv_batch_key_bound.restype = ctypes.c_double
+    L.sdbv_batch_key_bound.argtypes = [u8, u32, ctypes.c_double,
+                                       ctypes.c_double]
     L.sdbv_bf16_rne.restype = ctypes.c_float
     L.sdbv_bf16_rne.argtypes = [ctypes.c_float]
     L.sdbv_knn_bruteforce.argtypes = [vp, u64, f32p, u32, u32, u64p, f64p, u32p]
@@ -419,6 +424,14 @@ def filter_rows(allow, n, cap=None):
 def prefilter_eps(d):
     """Proven bound on |exact - prefilter| cosine distance at dimension d."""
     return float(lib().sdbv_prefilter_eps(d))
+
+
+def batch_key_bound(metric, d, q_norm, max_row_norm=0.0):
+    """Proven bound on |key - E| of knn_batch's window certificate
+    (host-only): key the f32 selection key under any summation order, E the
+    exact distance mapped into the key's domain (see sdbv.h)."""
+    return float(lib().sdbv_batch_key_bound(METRICS[metric], d, float(q_norm),
+                                            float(max_row_norm)))
 
 
 def prefilter_i8_row(x, norm):

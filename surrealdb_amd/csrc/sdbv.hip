@@ -122,7 +122,11 @@ struct Table {
 	float *cm = nullptr;      // [d][n_pad] feature-major
 	double *norms = nullptr;  // per-row f64 norm (cosine only)
 	float *aux = nullptr;     // per-row f32 selection key aux for the batch
-	                          // path: cosine 1/norm, euclidean sum-of-squares
+	                          // path: cosine 1/norm, euclidean sum-of-squares;
+	                          // NaN marks a row without a usable key
+	uint32_t *bunc = nullptr; // [BATCH_UNC_CAP] rows without a usable key
+	uint32_t bunc_n = 0;      // their count (may exceed the list's capacity)
+	double bmax_norm = 0.0;   // largest norm among the rows with a key
 	uint64_t *ids_dev = nullptr; // per-row id, device (merge kernel maps)
 	Shadow sh;
 	uint64_t bytes = 0;
@@ -2293,17 +2297,35 @@ __global__ void k_binit(BCand *state, uint64_t total) {
 	}
 }
 
+// What staging learns about a table for the batch path besides aux.
+struct BatchAuxHdr {
+	unsigned long long max_norm_bits; // largest norm of a row with a key (f64
+	                                  // bits: non-negative doubles order as u64)
+	uint32_t n_unc;                   // rows without a usable key
+	uint32_t pad;
+};
+// Rows without a usable key the batch call lists and recomputes exactly for
+// every query; a table with more of them is answered by the exact scan.
+#define BATCH_UNC_CAP 1024u
+
 // f32 aux for the selection key: cosine -> 1/norm, euclidean -> restated f32
-// sum-of-squares per row.
+// sum-of-squares per row. A row the key bound (batch_key_bound) cannot cover
+// -- norm non-finite or above PF_NORM_MAX, for cosine also below PF_NORM_MIN,
+// zero included -- gets aux = NaN, which makes its key NaN for every query, and
+// is appended to unc_rows (in no particular order).
 __global__ void k_aux(const float *__restrict__ cm,
                       const double *__restrict__ norms,
                       float *__restrict__ aux, uint64_t n, uint64_t n_pad,
-                      uint32_t d, int metric) {
+                      uint32_t d, int metric, uint32_t *__restrict__ unc_rows,
+                      BatchAuxHdr *__restrict__ hdr) {
 	uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
 	if (r >= n)
 		return;
+	float a;
+	double norm;
 	if (metric == 0) {
-		aux[r] = (float)(1.0 / norms[r]);
+		norm = norms[r];
+		a = (float)(1.0 / norm);
 	} else {
 		float p[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 		uint32_t k = 0;
@@ -2323,7 +2345,20 @@ __global__ void k_aux(const float *__restrict__ cm,
 			float x = cm[(uint64_t)k * n_pad + r];
 			acc = __fadd_rn(acc, __fmul_rn(x, x));
 		}
-		aux[r] = acc;
+		a = acc;
+		norm = sqrt((double)acc);
+	}
+	const bool covered =
+	    norm <= PF_NORM_MAX && (metric != 0 || norm >= PF_NORM_MIN);
+	if (covered) {
+		aux[r] = a;
+		atomicMax(&hdr->max_norm_bits,
+		          (unsigned long long)__double_as_longlong(norm));
+	} else {
+		aux[r] = __uint_as_float(0x7FC00000u);
+		uint32_t idx = atomicAdd(&hdr->n_unc, 1u);
+		if (idx < BATCH_UNC_CAP)
+			unc_rows[idx] = (uint32_t)r;
 	}
 }
 
@@ -2406,6 +2441,8 @@ __global__ __launch_bounds__(THREADS) void k_batch_topk(
 					continue;
 				float key = (metric == 0) ? -(sv[c] * aux[r])
 				                          : (aux[r] - 2.0f * sv[c]);
+				if (key != key)
+					continue; // a row without a usable key (aux = NaN)
 				uint64_t tk = d_total_key32(key);
 				uint32_t row32 = (uint32_t)r;
 				bool take =
@@ -2460,7 +2497,8 @@ __global__ __launch_bounds__(THREADS) void k_batch_topk(
 // query's bootstrapped kth-best threshold) append to a per-query candidate
 // buffer; the b x n score matrix NEVER touches HBM (the round-1 rocBLAS +
 // k_batch_topk path re-read ~41 GB/step of it). Thresholds bootstrap on the
-// first rows via the legacy path, so expected appends/query ~ kk*ln(n/n0).
+// first n0 rows via the legacy path and stay put during the launch, so a
+// query appends about kk*(n/n0 - 1) candidates (~1200 at 3M rows).
 // Selection semantics are identical to k_batch_topk (exact running top-kk
 // by (monotone f32 key, row)): the filter can only drop entries strictly
 // worse than the current kk-th, and k_cand_fold recomputes the exact
@@ -2587,7 +2625,8 @@ __global__ __launch_bounds__(256) void k_mfma_scan_topk(
 				float key = (metric == 0) ? -(s * aux[row])
 				                          : (aux[row] - 2.0f * s);
 				uint32_t tk = (uint32_t)d_total_key32(key);
-				if (tk <= th) {
+				// key != key: a row without a usable key (aux = NaN)
+				if (tk <= th && key == key) {
 					uint32_t idx = atomicAdd(&cand_cnt[j], 1u);
 					if (idx < FMM_CAND_CAP) {
 						cand[(uint64_t)j * FMM_CAND_CAP + idx] =
@@ -2650,12 +2689,18 @@ __global__ __launch_bounds__(THREADS) void k_cand_fold(
 		kth_row = topk[kk - 1].row;
 	}
 	__syncthreads();
+	// a tile is TILE candidates, ROWS_PER_LANE per thread (one per thread
+	// left three quarters of every tile unread: wrong results from 257
+	// candidates on)
 	for (uint32_t tile = 0; tile < m_in; tile += TILE) {
-		uint32_t i = tile + threadIdx.x;
 		uint64_t kk_key = kth_key;
 		uint32_t kk_row = kth_row;
 		int full = (topk_n >= kk);
-		if (i < m_in) {
+#pragma unroll
+		for (uint32_t l = 0; l < ROWS_PER_LANE; l++) {
+			uint32_t i = tile + l * THREADS + threadIdx.x;
+			if (i >= m_in)
+				break;
 			BCand c = cj[i];
 			uint64_t tk = d_total_key32(c.key);
 			bool take = !full || tk < kk_key ||
@@ -2707,13 +2752,17 @@ __global__ void k_batch_exact(const float *__restrict__ cm,
                               uint64_t n_pad, uint32_t d,
                               const float *__restrict__ Q,
                               const double *__restrict__ qnorms, int metric,
-                              const BCand *__restrict__ state, int kk,
+                              const BCand *__restrict__ state,
+                              const uint32_t *__restrict__ shared_rows, int kk,
                               double *__restrict__ out) {
 	uint32_t j = blockIdx.x;  // query
 	uint32_t c = blockIdx.y;  // candidate slot
 	if (threadIdx.x != 0)
 		return;
-	BCand cand = state[(uint64_t)j * kk + c];
+	// shared_rows: the same kk rows for every query (the rows without a
+	// usable key) in place of the query's own window
+	BCand cand = shared_rows ? BCand{0.f, shared_rows[c]}
+	                         : state[(uint64_t)j * kk + c];
 	double *o = out + (uint64_t)j * kk + c;
 	if (cand.row == ~0u) {
 		*o = __longlong_as_double(0x7FF0000000000000LL);
@@ -3273,6 +3322,8 @@ static void free_table(Table &t) {
 		(void)hipFree(t.norms);
 	if (t.aux)
 		(void)hipFree(t.aux);
+	if (t.bunc)
+		(void)hipFree(t.bunc);
 	if (t.ids_dev)
 		(void)hipFree(t.ids_dev);
 	if (t.sh.codes)
@@ -3555,21 +3606,35 @@ static int staged_shadow_kind(const Table *t) {
 
 static int finish_stage(sdbv_ctx *ctx, Table *t, bool scan_table) {
 	uint64_t nb = (t->n + THREADS - 1) / THREADS;
+	BatchAuxHdr *hdr = nullptr;
 	if (t->metric == SDBV_METRIC_COSINE) {
 		hipLaunchKernelGGL(k_norms, dim3((uint32_t)nb), dim3(THREADS), 0,
 		                   ctx->stream, t->cm, t->norms, t->n, t->n_pad, t->d);
 	}
 	if (t->metric <= SDBV_METRIC_EUCLIDEAN) {
-		// batch-path selection aux (cosine 1/norm, euclidean sumsq); the
+		// batch-path selection aux (cosine 1/norm, euclidean sumsq), the rows
+		// without a usable key and the largest norm of the others; the
 		// other metrics take the all-distances route and need none
 		HIP_CHECK(ctx, hipMalloc(&t->aux, t->n_pad * sizeof(float)));
 		t->bytes += t->n_pad * sizeof(float);
+		const uint64_t unc_bytes =
+		    BATCH_UNC_CAP * sizeof(uint32_t) + sizeof(BatchAuxHdr);
+		// (a fixed 4 KiB, left out of the per-row byte count)
+		HIP_CHECK(ctx, hipMalloc(&t->bunc, unc_bytes));
+		hdr = (BatchAuxHdr *)(t->bunc + BATCH_UNC_CAP);
+		HIP_CHECK(ctx, hipMemsetAsync(hdr, 0, sizeof(BatchAuxHdr), ctx->stream));
 		hipLaunchKernelGGL(k_aux, dim3((uint32_t)nb), dim3(THREADS), 0,
 		                   ctx->stream, t->cm, t->norms, t->aux, t->n,
-		                   t->n_pad, t->d, (int)t->metric);
+		                   t->n_pad, t->d, (int)t->metric, t->bunc, hdr);
 	}
 	HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
 	HIP_CHECK(ctx, hipGetLastError());
+	if (hdr) {
+		BatchAuxHdr h;
+		HIP_CHECK(ctx, hipMemcpy(&h, hdr, sizeof(h), hipMemcpyDeviceToHost));
+		t->bunc_n = h.n_unc;
+		std::memcpy(&t->bmax_norm, &h.max_norm_bits, sizeof(double));
+	}
 	refresh_bytes_staged(ctx);
 	// a table staged for scanning gets the prefilter shadow when the policy
 	// asks for one; without the memory for it the table simply has none
@@ -3664,6 +3729,24 @@ int sdbv_table_set_prefilter_i6(sdbv_ctx *ctx, uint64_t table) {
 }
 
 float sdbv_prefilter_eps(uint32_t d) { return pf_eps(d); }
+
+// Proven bound on |key - E| of the batch path: key is the
+// f32 selection key of a row under ANY summation order of the two f32 dot
+// products, E the row's exact distance mapped into the key's domain in f64,
+//   cosine:    key = -(s * f32(1 / norm)),  E = -(1 - dist) * q_norm
+//   euclidean: key = sumsq - 2 s,           E = dist^2 - q_norm^2
+// with gamma(m) = m u / (1 - m u), u = 2^-24. Holds for rows and queries with
+// norms in [PF_NORM_MIN, PF_NORM_MAX] (euclidean: at most PF_NORM_MAX);
+// max_row_norm is the largest such row norm of the table (euclidean only).
+double sdbv_batch_key_bound(uint8_t metric, uint32_t d, double q_norm,
+                            double max_row_norm) {
+	const double u = 0x1p-24;
+	auto gamma = [u](double m) { return m * u / (1.0 - m * u); };
+	if (metric == SDBV_METRIC_COSINE)
+		return 1.01 * (2.0 * gamma(d + 1.0) + 3.0 * u) * q_norm;
+	const double w = (max_row_norm + q_norm) * (max_row_norm + q_norm);
+	return 1.01 * (3.0 * gamma(d + 2.0) + 2.0 * u) * w + 4.0 * d * 0x1p-149;
+}
 
 int sdbv_prefilter_i8_row(const float *x, uint32_t d, double norm,
                           int8_t *codes, float *scale, float *eps) {
@@ -4793,6 +4876,33 @@ int sdbv_knn_batch(sdbv_ctx *ctx, uint64_t table, const float *Q, uint32_t b,
 		return SDBV_OK;
 	}
 	const int kk = (int)k + BATCH_SLACK;
+	ctx->stats.last_batch_exact_queries = 0;
+	ctx->stats.last_batch_refold = 0;
+
+	// Which queries the window serves, which the exact scan (to_exact): a
+	// query whose norm the key bound does not cover (zero, non-finite, outside
+	// the window's norm range) goes there at once, and so does every query
+	// of a table with more rows without a usable key than the list holds;
+	// the others only if their window fails its certificate below.
+	// The norms are k_qnorms' (the chain of h_sumsq_f32), read back at the
+	// call's first synchronisation.
+	std::vector<double> h_qnorm(b);
+	std::vector<uint8_t> to_exact(b, 0);
+	bool qnorms_read = false;
+	auto read_qnorms = [&]() -> int {
+		if (qnorms_read)
+			return SDBV_OK;
+		qnorms_read = true;
+		HIP_CHECK(ctx, hipMemcpyAsync(h_qnorm.data(), ctx->qnorms,
+		                              b * sizeof(double),
+		                              hipMemcpyDeviceToHost, ctx->stream));
+		HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+		for (uint32_t j = 0; j < b; j++)
+			if (!(h_qnorm[j] >= PF_NORM_MIN && h_qnorm[j] <= PF_NORM_MAX) ||
+			    t.bunc_n > BATCH_UNC_CAP)
+				to_exact[j] = 1;
+		return SDBV_OK;
+	};
 
 	if (!ctx->blas) {
 		if (rocblas_create_handle(&ctx->blas) != rocblas_status_success) {
@@ -4819,8 +4929,11 @@ int sdbv_knn_batch(sdbv_ctx *ctx, uint64_t table, const float *Q, uint32_t b,
 	if ((rc = ensure_cap(ctx, (void **)&ctx->qnorms, &ctx->qnorms_cap,
 	                     (uint64_t)b * sizeof(double))))
 		return rc;
+	// rows without a usable key that every window query recomputes exactly
+	const uint32_t n_unc = t.bunc_n <= BATCH_UNC_CAP ? t.bunc_n : 0;
 	if ((rc = ensure_cap(ctx, (void **)&ctx->bdists, &ctx->bdists_cap,
-	                     (uint64_t)b * kk * sizeof(double))))
+	                     (uint64_t)b * std::max<uint32_t>(kk, n_unc) *
+	                         sizeof(double))))
 		return rc;
 
 	HIP_CHECK(ctx, hipMemcpyAsync(ctx->Q_dev, Q,
@@ -4923,15 +5036,26 @@ int sdbv_knn_batch(sdbv_ctx *ctx, uint64_t table, const float *Q, uint32_t b,
 		(void)hipEventElapsedTime(&m1, ctx->ev1, ctx->ev2);
 		ms_gemm += m0;
 		ms_select += m1;
+		if ((rc = read_qnorms()))
+			return rc;
 		bool overflow = false;
+		// (the window of a query bound for the exact scan is never read)
 		for (uint32_t j = 0; j < b; j++)
-			if (h_cnt[j] > FMM_CAND_CAP)
+			if (h_cnt[j] > FMM_CAND_CAP && !to_exact[j])
 				overflow = true;
 		if (overflow) {
-			// a candidate buffer filled (adversarially ordered corpus):
-			// re-present the fused rows through the legacy pass — state
-			// merging is exact, so dropped appends are recovered
-			if ((rc = legacy_rows(fused_row0, t.n)))
+			// a candidate buffer filled (adversarially ordered corpus), so
+			// appends were dropped: start every state over and run ALL rows
+			// through the legacy pass. Presenting only the fused rows on
+			// top of the folded state would take the rows already in it a
+			// second time (neither k_batch_topk nor block_select_topk
+			// deduplicates).
+			ctx->stats.last_batch_refold = 1;
+			uint64_t total = (uint64_t)b * kk;
+			hipLaunchKernelGGL(k_binit, dim3((uint32_t)((total + 255) / 256)),
+			                   dim3(256), 0, ctx->stream, (BCand *)ctx->bstate,
+			                   total);
+			if ((rc = legacy_rows(0, t.n)))
 				return rc;
 		}
 	}
@@ -4940,8 +5064,8 @@ int sdbv_knn_batch(sdbv_ctx *ctx, uint64_t table, const float *Q, uint32_t b,
 	HIP_CHECK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
 	hipLaunchKernelGGL(k_batch_exact, dim3(b, kk), dim3(64), 0, ctx->stream,
 	                   t.cm, t.norms, t.n_pad, t.d, ctx->Q_dev, ctx->qnorms,
-	                   (int)t.metric, (const BCand *)ctx->bstate, kk,
-	                   ctx->bdists);
+	                   (int)t.metric, (const BCand *)ctx->bstate,
+	                   (const uint32_t *)nullptr, kk, ctx->bdists);
 	HIP_CHECK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
 
 	std::vector<BCand> h_state((uint64_t)b * kk);
@@ -4954,14 +5078,29 @@ int sdbv_knn_batch(sdbv_ctx *ctx, uint64_t table, const float *Q, uint32_t b,
 	                              hipMemcpyDeviceToHost, ctx->stream));
 	HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
 	HIP_CHECK(ctx, hipGetLastError());
+	if ((rc = read_qnorms()))
+		return rc;
 	float me = 0;
 	(void)hipEventElapsedTime(&me, ctx->ev0, ctx->ev1);
-	ctx->ms_gemm = ms_gemm;
-	ctx->ms_select = ms_select;
-	ctx->ms_exact = me;
-	ctx->stats.last_scan_kernel_ms = ms_gemm; // dominant kernel of the batch
-	ctx->stats.last_merge_kernel_ms = ms_select;
-	ctx->stats.last_rows_scanned = t.n;
+
+	// The rows without a usable key were kept out of every window: each
+	// query gets their exact distances as well (the same rows for all).
+	std::vector<uint32_t> h_unc(n_unc);
+	std::vector<double> h_unc_dists((uint64_t)b * n_unc);
+	if (n_unc) {
+		hipLaunchKernelGGL(k_batch_exact, dim3(b, n_unc), dim3(64), 0,
+		                   ctx->stream, t.cm, t.norms, t.n_pad, t.d, ctx->Q_dev,
+		                   ctx->qnorms, (int)t.metric, (const BCand *)nullptr,
+		                   (const uint32_t *)t.bunc, (int)n_unc, ctx->bdists);
+		HIP_CHECK(ctx, hipMemcpyAsync(h_unc.data(), t.bunc,
+		                              n_unc * sizeof(uint32_t),
+		                              hipMemcpyDeviceToHost, ctx->stream));
+		HIP_CHECK(ctx, hipMemcpyAsync(h_unc_dists.data(), ctx->bdists,
+		                              h_unc_dists.size() * sizeof(double),
+		                              hipMemcpyDeviceToHost, ctx->stream));
+		HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+		HIP_CHECK(ctx, hipGetLastError());
+	}
 
 	// final exact rank per query: ascending (total_cmp(dist), id)
 	std::vector<uint64_t> ids_host(t.n_pad);
@@ -4973,17 +5112,47 @@ int sdbv_knn_batch(sdbv_ctx *ctx, uint64_t table, const float *Q, uint32_t b,
 		std::memcpy(&bits, &x, 8);
 		return (bits >> 63) ? ~bits : (bits | 0x8000000000000000ULL);
 	};
-	std::vector<std::pair<std::pair<uint64_t, uint64_t>, double>> cand(kk);
+	std::vector<std::pair<std::pair<uint64_t, uint64_t>, double>> cand(kk +
+	                                                                   n_unc);
 	for (uint32_t j = 0; j < b; j++) {
+		if (to_exact[j])
+			continue;
 		size_t m = 0;
+		float bkey = -std::numeric_limits<float>::infinity();
 		for (int c = 0; c < kk; c++) {
 			BCand bc = h_state[(uint64_t)j * kk + c];
 			if (bc.row == ~0u)
 				continue;
 			double dd = h_dists[(uint64_t)j * kk + c];
 			cand[m++] = {{total_key(dd), ids_host[bc.row]}, dd};
+			bkey = std::max(bkey, bc.key);
 		}
 		std::sort(cand.begin(), cand.begin() + m);
+		// Window certificate. A window that is not full
+		// holds every row with a key. A full one holds every row whose key
+		// is below its largest key bkey; a row as near as the window's k-th
+		// nearest (exact distance dk, E(dk) in the key's domain) has a key
+		// of at most E(dk) + bound, so bkey above that proves that the
+		// k nearest rows with a key are all inside. E is monotone in the
+		// distance, in f64 as computed here.
+		if (m == (size_t)kk) {
+			const double dk = cand[k - 1].second, qn = h_qnorm[j];
+			const double ek = t.metric == SDBV_METRIC_COSINE
+			                      ? -((1.0 - dk) * qn)
+			                      : dk * dk - qn * qn;
+			const double bound =
+			    sdbv_batch_key_bound(t.metric, d, qn, t.bmax_norm);
+			if (!((double)bkey > ek + bound)) {
+				to_exact[j] = 1;
+				continue;
+			}
+		}
+		for (uint32_t c = 0; c < n_unc; c++) {
+			double dd = h_unc_dists[(uint64_t)j * n_unc + c];
+			cand[m++] = {{total_key(dd), ids_host[h_unc[c]]}, dd};
+		}
+		if (n_unc)
+			std::sort(cand.begin(), cand.begin() + m);
 		uint32_t out_m = (uint32_t)std::min<size_t>(k, m);
 		for (uint32_t c = 0; c < out_m; c++) {
 			out_ids[(uint64_t)j * k + c] = cand[c].first.second;
@@ -4995,6 +5164,44 @@ int sdbv_knn_batch(sdbv_ctx *ctx, uint64_t table, const float *Q, uint32_t b,
 			    std::numeric_limits<double>::infinity();
 		}
 	}
+
+	// The queries the window could not answer: the single-query exact scan.
+	uint64_t rows_per_block = 0;
+	const uint64_t nblocks = scan_grid(t.n, &rows_per_block);
+	bool scratch_ready = false;
+	for (uint32_t j = 0; j < b; j++) {
+		if (!to_exact[j])
+			continue;
+		if (!scratch_ready) {
+			if ((rc = ensure_query_scratch(ctx, d, nblocks, k)))
+				return rc;
+			scratch_ready = true;
+		}
+		const float *q = Q + (uint64_t)j * d;
+		if ((rc = stage_query(ctx, q, d, d * sizeof(float))))
+			return rc;
+		Cand host_out[MAX_K];
+		if ((rc = knn_exact_scan(ctx, t, k, h_qnorm[j], nblocks, rows_per_block,
+		                         host_out)))
+			return rc;
+		const uint32_t out_m = (uint32_t)std::min<uint64_t>(k, t.n);
+		for (uint32_t c = 0; c < out_m; c++) {
+			out_ids[(uint64_t)j * k + c] = host_out[c].id;
+			out_dists[(uint64_t)j * k + c] = host_out[c].dist;
+		}
+		for (uint32_t c = out_m; c < k; c++) {
+			out_ids[(uint64_t)j * k + c] = ~0ULL;
+			out_dists[(uint64_t)j * k + c] =
+			    std::numeric_limits<double>::infinity();
+		}
+		ctx->stats.last_batch_exact_queries++;
+	}
+	ctx->ms_gemm = ms_gemm;
+	ctx->ms_select = ms_select;
+	ctx->ms_exact = me;
+	ctx->stats.last_scan_kernel_ms = ms_gemm; // dominant kernel of the batch
+	ctx->stats.last_merge_kernel_ms = ms_select;
+	ctx->stats.last_rows_scanned = t.n;
 	return SDBV_OK;
 }
 } // extern "C"

@@ -2,7 +2,8 @@
 
 The batch path selects with a monotone f32 key but re-computes survivors with
 the exact restated chain, so final ids/ranks/distance-bits must equal the
-single-query path and the oracle exactly."""
+single-query path and the oracle exactly. On these ordinary corpora every
+window is certified: no query falls back to the single-query exact scan."""
 import numpy as np
 import pytest
 
@@ -19,6 +20,12 @@ def ctx():
     c.close()
 
 
+def assert_window_answered(ctx):
+    st = ctx.stats()
+    assert st["last_batch_exact_queries"] == 0
+    assert st["last_batch_refold"] == 0
+
+
 @pytest.mark.parametrize("metric", ["cosine", "euclidean"])
 @pytest.mark.parametrize("n,d,b,k", [(50_000, 768, 32, 10), (4096, 128, 7, 5),
                                      (300_000, 768, 64, 48)])
@@ -27,6 +34,7 @@ def test_batch_matches_oracle(ctx, metric, n, d, b, k):
     Q = oracle.gen_f32(0xBEEF, 0, b, d)
     ctx.stage_corpus(11, corpus, metric=metric)
     ids, dists = ctx.knn_batch(11, Q, k)
+    assert_window_answered(ctx)
     for j in range(b):
         oids, odists = oracle.topk_f32(metric, corpus, Q[j], k)
         assert np.array_equal(ids[j], oids), f"{metric} q{j}: ids differ"
@@ -39,6 +47,7 @@ def test_batch_equals_single_query_path(ctx):
     ctx.stage_synthetic(12, n, d, metric="cosine", seed=0x5DB1)
     Q = oracle.gen_f32(0xBEEF, 0, b, d)
     bids, bdists = ctx.knn_batch(12, Q, k)
+    assert_window_answered(ctx)
     for j in range(b):
         sids, sdists = ctx.knn_bruteforce(12, Q[j], k)
         assert np.array_equal(bids[j], sids)
@@ -51,6 +60,7 @@ def test_batch_n_smaller_than_k(ctx):
     Q = oracle.gen_f32(0x55, 0, 3, 16)
     ctx.stage_corpus(13, corpus, metric="cosine")
     ids, dists = ctx.knn_batch(13, Q, 10)
+    assert_window_answered(ctx)
     for j in range(3):
         oids, odists = oracle.topk_f32("cosine", corpus, Q[j], 10)
         assert np.array_equal(ids[j][:6], oids)
@@ -65,6 +75,7 @@ def test_batch_duplicates(ctx):
     Q = base[[3, 30, 49]].copy()
     ctx.stage_corpus(14, corpus, metric="euclidean")
     ids, dists = ctx.knn_batch(14, Q, 4)
+    assert_window_answered(ctx)
     for j, orig in enumerate([3, 30, 49]):
         assert ids[j][0] == orig and ids[j][1] == 1000 + orig
         assert dists[j][0] == 0.0 and dists[j][1] == 0.0
@@ -82,9 +93,11 @@ def test_fused_mfma_matches_oracle_and_legacy(ctx, metric):
     Q = oracle.gen_f32(0xBEEF, 0, b, d)
     ctx.stage_corpus(13, corpus, metric=metric)
     ids_f, dists_f = ctx.knn_batch(13, Q, k)       # fused (default)
+    assert_window_answered(ctx)
     os.environ["SDBV_BATCH_LEGACY"] = "1"
     try:
         ids_l, dists_l = ctx.knn_batch(13, Q, k)   # legacy
+        assert_window_answered(ctx)
     finally:
         del os.environ["SDBV_BATCH_LEGACY"]
     assert np.array_equal(ids_f, ids_l), f"{metric}: fused != legacy ids"
@@ -107,6 +120,7 @@ def test_fused_mfma_duplicate_ties(ctx):
     corpus[12_345] = Q[3]  # inside the bootstrap range
     ctx.stage_corpus(14, corpus, metric="euclidean")
     ids, dists = ctx.knn_batch(14, Q, k)
+    assert_window_answered(ctx)
     assert list(ids[3][:3]) == [12_345, 70_000, 100_001]
     assert dists[3][0] == 0.0 and dists[3][2] == 0.0
     oids, odists = oracle.topk_f32("euclidean", corpus, Q[3], k)
