@@ -104,7 +104,11 @@ typedef struct sdbv_stats {
 	                            again: 15 = two-stage int6 prefilter (plane H
 	                            streamed alone, survivors refined with plane
 	                            L), 16 = its candidate list overflowed, then
-	                            exact scan */
+	                            exact scan. Euclidean tables: 17 = l2 (int8)
+	                            prefilter, 18 = that overflowed, then exact
+	                            scan; sdbv_knn_bruteforce_filtered: 19 = l2
+	                            prefilter under the bitmap, 20 = that
+	                            overflowed, then masked scan */
 	uint64_t last_filter_rows; /* allowed rows of the last filtered call (for
 	                              such a call last_rows_scanned is the same
 	                              count) */
@@ -159,6 +163,12 @@ int sdbv_get_stats(sdbv_ctx *, sdbv_stats *out);
  * SDBV_SCAN_PREFILTER_H4 is not 0 carries 8 B per row more: the bound and
  * the code sum of its high-nibble plane read on its own, which the two-stage
  * path needs (see sdbv_knn_bruteforce).
+ * A EUCLIDEAN table (the default metric of DEFINE INDEX ... HNSW) of at
+ * least SDBV_SCAN_PREFILTER_L2_MIN_ROWS rows (environment, default 500000)
+ * gets the l2 shadow, d + 12 B per row more (+25 %), unless
+ * SDBV_SCAN_PREFILTER_L2 is 0 or the allocation fails. The pair is the
+ * euclidean tier's own: the SDBV_SCAN_PREFILTER* variables above never give
+ * a euclidean table a shadow, and these two never give a cosine table one.
  * A table holds at
  * most one shadow. The shadow never changes a result (see
  * sdbv_knn_bruteforce). Tables staged for graph search (sdbv_hnsw_finalize,
@@ -195,6 +205,13 @@ int sdbv_table_set_prefilter_kind(sdbv_ctx *, uint64_t table, int kind);
  * sdbv_table_set_prefilter; free it with sdbv_table_set_prefilter(.., 0) or
  * sdbv_table_set_prefilter_kind(.., 0). */
 int sdbv_table_set_prefilter_i6(sdbv_ctx *, uint64_t table);
+/* Build (on != 0) or free (on == 0) the l2 shadow of a staged EUCLIDEAN
+ * table, regardless of the staging policy: int8 codes as for kind 2 with
+ * three f32 values per row, the scale, the squared length of the dequantised
+ * row and the row's residual rounded up (d + 12 B per row).
+ * SDBV_ERR_UNSUPPORTED for every other metric (the three entries above keep
+ * refusing euclidean tables), SDBV_ERR_OOM when the shadow does not fit. */
+int sdbv_table_set_prefilter_l2(sdbv_ctx *, uint64_t table, int on);
 /* Host-only: the proven bound on |exact - prefilter| cosine distance at
  * dimension d, and f32 -> bf16 round-to-nearest-even (returned as f32) as
  * the shadow is built. */
@@ -220,6 +237,22 @@ double sdbv_batch_key_bound(uint8_t metric, uint32_t d, double q_norm,
  * prefilter always recomputes such a row. */
 int sdbv_prefilter_i8_row(const float *x, uint32_t d, double norm,
                           int8_t *codes, float *scale, float *eps);
+/* Host-only: quantise one row for the l2 shadow exactly as staging does.
+ * codes and *scale as for int8; with x^ = scale * codes, *xx = |x^|^2 computed
+ * in f64 and rounded once, *res = |x - x^| + 2^-68 computed in f64 and rounded
+ * UP (the 2^-68 stands for squares that underflow in the exact chain). A row
+ * the bound cannot cover (non-finite element, f64 norm above 2^30) gets zero
+ * codes, *scale = NaN, *xx = *res = 0. The zero row is covered. */
+int sdbv_prefilter_l2_row(const float *x, uint32_t d, int8_t *codes,
+                          float *scale, float *xx, float *res);
+/* Host-only: the interval the l2 stream computes for that row and the query
+ * q, with the kernel's own operations: *lo <= exact euclidean distance <=
+ * *up (-inf / +inf for an uncovered row). SDBV_ERR_UNSUPPORTED for a query
+ * outside the window (non-finite element, f64 norm above 2^30); the zero
+ * query is inside. */
+int sdbv_prefilter_l2_interval(const float *q, uint32_t d, const int8_t *codes,
+                               float scale, float xx, float res, float *lo,
+                               float *up);
 /* Host-only: the same for the int6 shadow. codes[k] = rint(x[k] / scale) in
  * [-31, 31], *scale = f32(maxabs / 31), *xsum = sum of the stored codes
  * (codes[k] + 32) over the row padded with zero codes to a multiple of 32
@@ -296,7 +329,16 @@ void sdbv_gen_f32(uint64_t seed, uint64_t row0, uint64_t nrows, uint32_t d,
  * ceiling 262144, read at each call), keeps of those the rows whose full
  * int6 lower bound is not above T, and recomputes these. A first list that
  * overflows hands the call to the plain int6 path (5 / 6); more than 16384
- * rows after the second test rerun the exact scan (16). */
+ * rows after the second test rerun the exact scan (16).
+ *
+ * On a euclidean table with the l2 shadow (k <= 64, finite query with an
+ * f64 norm of at most 2^30, the zero query included) the call streams the
+ * int8 codes and brackets every row's exact distance from the triangle
+ * inequality, [lo, up] around |scale * codes - q| widened by the row's
+ * residual and the proven rounding terms; it keeps every row whose lo does
+ * not exceed the Kth smallest up and recomputes those with the exact chain
+ * (last_scan_path 17; more than 16384 candidates rerun the exact scan, 18).
+ * The same exactness guarantee holds. */
 int sdbv_knn_bruteforce(sdbv_ctx *, uint64_t table, const float *q, uint32_t d,
                         uint32_t k, uint64_t *out_ids, double *out_dists,
                         uint32_t *out_n);
@@ -328,7 +370,9 @@ int sdbv_knn_bruteforce(sdbv_ctx *, uint64_t table, const float *q, uint32_t d,
  * (last_scan_path 9 bf16, 11 int8, 13 int6). A wave skips the rows of its
  * span when none of them is allowed: 512 rows (bf16), 1024 (int8), 64
  * (int6). More than 16384 candidates rerun the call as the masked scan
- * (10, 12, 14). Every other call runs the masked scan, k_scan with the
+ * (10, 12, 14). A euclidean table with the l2 shadow streams it under the
+ * same two variables, for a query inside that tier's window (19; 1024 rows
+ * per skipped wave span; overflow 20). Every other call runs the masked scan, k_scan with the
  * bitmap as a second validity test, which skips every 256-row segment
  * without an allowed row (last_scan_path 7). The shadow is only read: an
  * unfiltered call before or after is not disturbed. Other metrics and

@@ -46,6 +46,12 @@ class SdbvError(RuntimeError):
 
 
 class _Stats(ctypes.Structure):
+    """sdbv_stats (include/sdbv.h). last_scan_path: 0 exact scan; 1..6 the
+    cosine prefilter tiers (bf16, int8, int6; the even number = candidate
+    overflow, then exact scan); 7 masked scan, 8 row list, 9..14 the cosine
+    tiers under a filter; 15 / 16 the two-stage int6 path; 17 / 18 the
+    euclidean (l2) prefilter and its overflow, 19 / 20 the same under a
+    filter. last_prefilter_candidates: rows passed to the exact rescore."""
     _fields_ = [
         ("last_scan_kernel_ms", ctypes.c_double),
         ("last_merge_kernel_ms", ctypes.c_double),
@@ -97,6 +103,14 @@ def lib():
     L.sdbv_prefilter_i8_row.argtypes = [f32p, u32, ctypes.c_double,
                                         ctypes.POINTER(ctypes.c_int8), f32p,
                                         f32p]
+    L.sdbv_table_set_prefilter_l2.argtypes = [vp, u64, ctypes.c_int]
+    L.sdbv_prefilter_l2_row.argtypes = [f32p, u32,
+                                        ctypes.POINTER(ctypes.c_int8), f32p,
+                                        f32p, f32p]
+    L.sdbv_prefilter_l2_interval.argtypes = [f32p, u32,
+                                             ctypes.POINTER(ctypes.c_int8),
+                                             ctypes.c_float, ctypes.c_float,
+                                             ctypes.c_float, f32p, f32p]
     L.sdbv_prefilter_i6_row.argtypes = [f32p, u32, ctypes.c_double,
                                         ctypes.POINTER(ctypes.c_int8), f32p,
                                         f32p, ctypes.POINTER(ctypes.c_uint32)]
@@ -285,6 +299,13 @@ class Context:
         _check(self._ptr, lib().sdbv_table_set_prefilter_i6(
             self._ptr, table), "sdbv_table_set_prefilter_i6")
 
+    def table_set_prefilter_l2(self, table, on):
+        """Build (on) or free (off) the l2 prefilter shadow of a euclidean
+        table, regardless of the staging policy (SDBV_SCAN_PREFILTER_L2 /
+        SDBV_SCAN_PREFILTER_L2_MIN_ROWS); every other metric is refused."""
+        _check(self._ptr, lib().sdbv_table_set_prefilter_l2(
+            self._ptr, table, int(bool(on))), "sdbv_table_set_prefilter_l2")
+
     def knn_bruteforce(self, table, q, k):
         import numpy as np
         q = np.ascontiguousarray(q, dtype=np.float32)
@@ -311,8 +332,9 @@ class Context:
         the bitmap on a shadowed cosine table of at least
         SDBV_FILTER_PREFILTER_MIN_ROWS (500000) rows, k <= 64, unless
         SDBV_FILTER_PREFILTER=0 (9 / 11 / 13 by tier, the even number after
-        it when the candidate list overflowed); the masked exact scan
-        otherwise (7)."""
+        it when the candidate list overflowed), and likewise the l2 shadow
+        of a euclidean table (19 / 20); the masked exact scan otherwise
+        (7)."""
         import numpy as np
         q = np.ascontiguousarray(q, dtype=np.float32)
         n = self.table_rows(table)
@@ -448,6 +470,47 @@ def prefilter_i8_row(x, norm):
         codes.ctypes.data_as(ctypes.POINTER(ctypes.c_int8)),
         ctypes.byref(scale), ctypes.byref(eps)), "sdbv_prefilter_i8_row")
     return codes, np.float32(scale.value), np.float32(eps.value)
+
+
+def prefilter_l2_row(x):
+    """Quantise one f32 row for the euclidean (l2) prefilter shadow as
+    staging does (host-only): (codes int8[d], scale f32, xx f32, res f32).
+    xx is the squared length of scale * codes, res the row's residual
+    |x - scale * codes| + 2^-68 rounded up; scale is NaN for a row the bound
+    cannot cover."""
+    import numpy as np
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    codes = np.empty(x.size, dtype=np.int8)
+    scale = ctypes.c_float(0.0)
+    xx = ctypes.c_float(0.0)
+    res = ctypes.c_float(0.0)
+    _check(None, lib().sdbv_prefilter_l2_row(
+        x.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), x.size,
+        codes.ctypes.data_as(ctypes.POINTER(ctypes.c_int8)),
+        ctypes.byref(scale), ctypes.byref(xx), ctypes.byref(res)),
+        "sdbv_prefilter_l2_row")
+    return (codes, np.float32(scale.value), np.float32(xx.value),
+            np.float32(res.value))
+
+
+def prefilter_l2_interval(q, codes, scale, xx, res):
+    """(lo, up) f32 around the exact euclidean distance of the query q and
+    the row prefilter_l2_row described, with the stream kernel's own
+    operations (host-only); (-inf, +inf) for an uncovered row. Raises for a
+    query outside the window (non-finite, norm above 2^30)."""
+    import numpy as np
+    q = np.ascontiguousarray(q, dtype=np.float32)
+    codes = np.ascontiguousarray(codes, dtype=np.int8)
+    if codes.size != q.size:
+        raise SdbvError(f"codes: {codes.size} entries for d = {q.size}")
+    lo = ctypes.c_float(0.0)
+    up = ctypes.c_float(0.0)
+    _check(None, lib().sdbv_prefilter_l2_interval(
+        q.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), q.size,
+        codes.ctypes.data_as(ctypes.POINTER(ctypes.c_int8)),
+        float(scale), float(xx), float(res),
+        ctypes.byref(lo), ctypes.byref(up)), "sdbv_prefilter_l2_interval")
+    return np.float32(lo.value), np.float32(up.value)
 
 
 def prefilter_i6_row(x, norm):

@@ -20,6 +20,10 @@ CMD = [
     "--offload-arch=gfx950",
     "-O3",
     "-ffp-contract=off",
+    # The l2 prefilter's proof (pf_l2_finish) needs the device's f32 sqrt
+    # correctly rounded, as the host's is. It is the compiler's default for
+    # HIP; spelled out because a bound rests on it.
+    "-fhip-fp32-correctly-rounded-divide-sqrt",
     # AVX2 for the HOST build path (graph construction distance chains).
     # Bit-exactness holds: the restated unrolled-8 chain keeps 8 independent
     # sequential partials, which vectorize to one 8-lane register without

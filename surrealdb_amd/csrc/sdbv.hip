@@ -92,8 +92,13 @@
 //    pscale, peps, then xsum (the row's sum of stored codes); with h4 also
 //    peps4 and xsum_h, the bound and the code sum of plane H read on its own
 //    (the two-stage path).
+// A euclidean table has one tier, with an index of its own (4 is taken by
+// the int6 H-only grid entry of SHADOW_TIERS and pf_slots):
+//  5 l2: codes as int8; side = the scale (NaN marks an uncovered row), then
+//    xx = |scale * c|^2, then res, the row's residual rounded up
+//    (DESIGN.md §11e).
 struct Shadow {
-	int kind = 0;          // 0 none, 1 bf16, 2 int8, 3 int6
+	int kind = 0;          // 0 none, 1 bf16, 2 int8, 3 int6, 5 l2
 	bool h4 = false;       // int6 only: side holds peps4 and xsum_h too
 	void *codes = nullptr; // owning
 	float *side = nullptr; // owning: sn_pad floats per side array
@@ -102,6 +107,9 @@ struct Shadow {
 	float *pinv() const { return side; }
 	float *pscale() const { return side; }
 	float *peps() const { return side + sn_pad; }
+	// l2: the stream kernel finds res sn_pad floats behind xx
+	float *l2_xx() const { return side + sn_pad; }
+	float *l2_res() const { return side + 2 * sn_pad; }
 	uint32_t *xsum() const { return (uint32_t *)(side + 2 * sn_pad); }
 	float *peps4() const { return h4 ? side + 3 * sn_pad : nullptr; }
 	uint32_t *xsum_h() const {
@@ -157,7 +165,7 @@ struct sdbv_ctx {
 	void *pf4_thr = nullptr;      // [MAX_K] Cand: its threshold rows, exact
 	void *pf_cands = nullptr;    // [PF_CAND_CAP] rescored Cand
 	void *pf_res = nullptr;      // [MAX_K + 2] Cand: top-k, the count, counter
-	uint64_t pf_slots[2][5] = {}; // by MASKED and Shadow::kind (4 = the int6
+	uint64_t pf_slots[2][6] = {}; // by MASKED and Shadow::kind (4 = the int6
 	                              // tier's H-only stream): blocks of that
 	                              // prefilter kernel the device holds at once
 	// batched path
@@ -1113,6 +1121,228 @@ __global__ void k_shadow_i8(const float *__restrict__ cm,
 	peps[r] = pe;
 }
 
+// ---------------------------------------------------------------------------
+// Euclidean int8 tier (Shadow::kind 5): the codes and the
+// stream of the cosine int8 tier, three f32 side values per row (scale, xx,
+// res) and an interval [lo, up] around the exact distance from the triangle
+// inequality. With x^ = scale * c the dequantised row, D = |x - q| and
+// D^ = |x^ - q| in the reals, |D - D^| <= |x - x^|.
+// ---------------------------------------------------------------------------
+
+// e > 0 finite, rounded up to f32.
+__host__ __device__ static inline float pf_round_up_f32(double e) {
+	float ef = (float)e;
+	if ((double)ef < e)
+		ef = __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, ef) + 1u);
+	return ef;
+}
+
+// The query's constants of the euclidean finish, computed on the host in f64
+// and rounded once (pf_l2_query); they ride behind the query in ctx->q_dev.
+struct PfL2Q {
+	float qbias; // f32(128 sum q)
+	float qq;    // f32(|q|^2)
+	float c1;    // delta's factor of the row's scale, rounded up
+	float c2;    // delta's factor of xx + qq
+	float kl;    // 1 - rel, rounded down
+	float ku;    // 1 + rel, rounded up
+};
+#define PF_L2_C2 0x1.5p-21f  /* 10.5 u */
+#define PF_L2_C3 0x1p-112f   /* delta's absolute part */
+#define PF_L2_RES_ABS 0x1p-68 /* res carries this much more than |x - x^| */
+
+// Quantise one row for the euclidean int8 shadow (elements x[k * xstride],
+// k < d). The one routine behind both k_shadow_l2 and sdbv_prefilter_l2_row.
+// Codes and scale as pf_i8_row: scale = f32(maxabs / 127), c_k = rint(x_k /
+// scale) clamped to +-127, stored as bias-128 bytes at codes[k * cstride].
+// *xx = |x^|^2 and *res = |x - x^| + PF_L2_RES_ABS are computed in f64 from
+// the f32 elements and the products scale * c_k (31 significant bits: exact
+// in f64); their d + 3 f64 roundings are below 2^-40 relative. xx is rounded
+// once to f32, res is rounded UP.
+// Window: finite elements and an f64 norm sqrt(sum x_k^2) <= PF_NORM_MAX. A
+// row outside it is uncovered: neutral codes (byte 128), scale = NaN, xx =
+// res = 0, and the prefilter always rescores it. There is no lower limit:
+// the zero row is covered (scale = xx = 0, zero codes, x^ = x exactly), and
+// so is a row whose squares underflow, because every term of the bound below
+// keeps an absolute part for it.
+__host__ __device__ static inline void pf_l2_row(
+    const float *x, uint64_t xstride, uint32_t d, uint8_t *codes,
+    uint64_t cstride, float *scale, float *xx, float *res) {
+	float m = 0.f;
+	double n2 = 0.0;
+	bool bad = false;
+	for (uint32_t k = 0; k < d; k++) {
+		const float v = x[(uint64_t)k * xstride];
+		if ((__builtin_bit_cast(uint32_t, v) & 0x7F800000u) == 0x7F800000u)
+			bad = true;
+		m = fmaxf(m, fabsf(v));
+		n2 += (double)v * (double)v;
+	}
+	if (bad || !(n2 <= PF_NORM_MAX * PF_NORM_MAX)) {
+		for (uint32_t k = 0; k < d; k++)
+			codes[(uint64_t)k * cstride] = 128;
+		*scale = __builtin_bit_cast(float, 0x7FC00000u);
+		*xx = *res = 0.f;
+		return;
+	}
+	const float sc = (float)((double)m / 127.0);
+	const double sd = (double)sc;
+	double res2 = 0.0, xx2 = 0.0;
+	for (uint32_t k = 0; k < d; k++) {
+		const double xv = (double)x[(uint64_t)k * xstride];
+		// sd == 0: maxabs below 127 * 2^-150 rounds the scale to zero (the
+		// zero row included); every code is 0 and the row is its residual
+		double c = sd > 0.0 ? rint(xv / sd) : 0.0;
+		c = c > 127.0 ? 127.0 : (c < -127.0 ? -127.0 : c);
+		const double xh = sd * c;
+		const double r = xv - xh;
+		res2 += r * r;
+		xx2 += xh * xh;
+		codes[(uint64_t)k * cstride] = (uint8_t)((int)c + 128);
+	}
+	*scale = sc;
+	*xx = (float)xx2;
+	*res = pf_round_up_f32(sqrt(res2) * (1.0 + 0x1p-40) + PF_L2_RES_ABS);
+}
+
+// The query side: false for a query outside the window (a non-finite
+// element, or |q| above PF_NORM_MAX), which takes the exact scan. No lower
+// limit: the zero query is covered (t = qbias = qq = 0 and A2 = xx).
+// |q|_1, |q|^2 and sum q are f64 sums of f32 values (d + 1 roundings of
+// 2^-53 each, far inside the slack of the constants).
+__host__ __device__ static inline bool pf_l2_query(const float *q, uint32_t d,
+                                                   PfL2Q *c) {
+	double q1 = 0.0, q2 = 0.0, qs = 0.0;
+	bool bad = false;
+	for (uint32_t k = 0; k < d; k++) {
+		if ((__builtin_bit_cast(uint32_t, q[k]) & 0x7F800000u) == 0x7F800000u)
+			bad = true;
+		const double v = (double)q[k];
+		q1 += fabs(v);
+		q2 += v * v;
+		qs += v;
+	}
+	if (bad || !(q2 <= PF_NORM_MAX * PF_NORM_MAX))
+		return false;
+	const double u = 0x1p-24;
+	const double g = (double)(d + 2) * u / (1.0 - (double)(d + 2) * u);
+	c->qbias = (float)(128.0 * qs);
+	c->qq = (float)q2;
+	const double c1 = 2.01 * (double)(d + 2) * u * 255.0 * q1;
+	c->c1 = c1 > 0.0 ? pf_round_up_f32(c1) : 0.f;
+	c->c2 = PF_L2_C2;
+	const double kl = 1.0 - (0.5001 * g + 3.0 * u); // in (0.999, 1)
+	float klf = (float)kl;
+	if ((double)klf > kl) // round down: the f32 below
+		klf = __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, klf) - 1u);
+	c->kl = klf;
+	c->ku = pf_round_up_f32(1.0 + 0.5 * g + 3.0 * u);
+	return true;
+}
+
+// The finish of the euclidean stream, one row: the one routine behind both
+// k_prefilter_i8<., true> and sdbv_prefilter_l2_interval. t = the sequential
+// f32 FMA chain over b_k q_k (b_k the stored bytes). Returns A2; the caller
+// treats a non-finite A2 (an uncovered row: scale NaN) as no bound.
+//   w  = t - qbias                  a     = xx + qq
+//   A2 = fma(-2 scale, w, a)        delta = fma(scale, c1, fma(a, c2, C3))
+//   lo = max(0, sqrt(max(0, A2 - delta)) - res) * kl
+//   up = (sqrt(A2 + delta) + res) * ku
+// Every operation below is one f32 operation written out (fmaf, or a single
+// + - * that -ffp-contract=off keeps single), so host and device agree bit
+// for bit. sqrtf must be correctly rounded on the device as on the host: the
+// build passes -fhip-fp32-correctly-rounded-divide-sqrt and no fast-math
+// flag. f32 subnormals are kept, not flushed (the compiler's default for
+// gfx9; the build passes no -fgpu-flush-denormals-to-zero).
+//
+// Claim: lo <= exact <= up for a covered row and a query in the window,
+// exact = the chain of k_scan<1, .>: acc = the sequential f32 sum of
+// fl(fl(x_k - q_k)^2), exact = sqrt((double)acc). With u = 2^-24, gamma(m) =
+// m u / (1 - m u), X = |x^|^2, Q = |q|^2, C = sum c_k q_k in the reals, so
+// that D^^2 = X + Q - 2 scale C exactly (scale the stored f32). Every f32
+// result fl(z) is within u |z| of z, or within 2^-150 when it is subnormal
+// (sums and differences are then exact).
+//  - t: d FMA roundings on terms b_k |q_k| <= 255 |q_k|: |t - sum b_k q_k|
+//    <= gamma(d) 255 |q|_1 <= 1.001 d u 255 |q|_1. qbias is an f64 sum
+//    rounded once: within 1.001 u 128 |q|_1 of 128 sum q. w rounds once on
+//    |t - qbias| <= 1.01 * 127 |q|_1. Together |w - C| <= e_w =
+//    1.001 (d + 2) u 255 |q|_1, as for pf_i8_row, with |q|_1 the query's
+//    own, not sqrt(d) |q|.
+//  - a: xx and qq are each within 1.001 u of X and Q, the sum rounds once:
+//    |a - (X + Q)| <= 2.01 u (X + Q).
+//  - A2: -2 scale is exact, the FMA rounds z = a - 2 scale w once, and
+//    |z| <= D^^2 + |z - D^^2|, D^^2 <= 2 (X + Q):
+//    |A2 - D^^2| <= (1 + u) (2.01 u (X + Q) + 2 scale e_w) + 2 u (X + Q)
+//               <= 4.011 u (X + Q) + 2.0021 (d + 2) u 255 |q|_1 scale.
+//  - underflow: the d + 2 roundings behind w add at most 2^-150 each, times
+//    2 scale (1 + u) < 2^25 (scale <= 2^30 / 127); xx, qq and A2 add 2^-150
+//    each: below 2^-113 in all.
+//  - the roots: delta carries 6.02 u (X + Q) more than the above, which is
+//    >= 3.01 u D^^2. Then fl(A2 - delta) (1 + u)^2 <= D^^2 and
+//    fl(A2 + delta) (1 - u)^2 >= D^^2, so the correctly rounded roots obey
+//    sqrtf(fl(max(0, A2 - delta))) <= D^ <= sqrtf(fl(A2 + delta)). (A
+//    root of a subnormal is normal: no absolute part.)
+//  - delta itself: c1 = 2.01 (d + 2) u 255 |q|_1 rounded up (0.4 % above
+//    2.0021), c2 = 10.5 u against the 10.031 u needed, relative to a >=
+//    (X + Q) (1 - 2.01 u), C3 = 2^-112 against 2^-113: each slack exceeds
+//    the two FMA roundings of delta (its value is >= C3, so normal).
+//  - the exact chain: acc is a sum of d non-negative terms, each carrying
+//    the roundings of one difference (twice) and one product, then at most
+//    d - 1 additions: acc = D^2 (1 + theta), |theta| <= gamma(d + 2), plus
+//    at most d 2^-150 <= 2^-138 for products that underflow (differences
+//    and sums in the subnormal range are exact). The f64 root is correctly
+//    rounded: exact is within D sqrt(1 -+ gamma(d + 2)) -+ 2^-69, times
+//    1 -+ 2^-53. res carries PF_L2_RES_ABS = 2^-68 more than |x - x^|, so
+//    with D <= D^ + |x - x^| and D >= D^ - |x - x^|:
+//      exact <= (D^ + res) (1 + gamma / 2) (1 + 2^-53)
+//      exact >= (D^ - res) (1 - 0.5001 gamma) (1 - 2^-53)   when D^ > res.
+//  - the finish: the sum root + res and the product with ku round once each
+//    (res >= 2^-68 keeps them normal), so up >= (D^ + res) ku (1 - u)^2, and
+//    ku = 1 + gamma / 2 + 3 u rounded up covers it. The difference root -
+//    res and the product with kl round once each, lo <= (D^ - res) kl
+//    (1 + u)^2 + 2^-150, kl = 1 - (0.5001 gamma + 3 u) rounded down; the
+//    2^-150 of a subnormal product is inside the 2^-69 that res has in
+//    hand. A root at or below res gives lo = 0 <= exact.
+// Nothing overflows: |t| <= 255 sqrt(d) 2^30 < 2^45, scale |w| < 2^69,
+// xx, qq <= 2^61, up < 2^33.
+__host__ __device__ static inline float pf_l2_finish(float t, float scale,
+                                                     float xx, float res,
+                                                     const PfL2Q &c, float *lo,
+                                                     float *up) {
+	const float w = t - c.qbias;
+	const float a = xx + c.qq;
+	const float A2 = fmaf(-2.0f * scale, w, a);
+	const float delta = fmaf(scale, c.c1, fmaf(a, c.c2, PF_L2_C3));
+	const float rl = sqrtf(fmaxf(A2 - delta, 0.f));
+	const float ru = sqrtf(A2 + delta);
+	*lo = fmaxf(rl - res, 0.f) * c.kl;
+	*up = (ru + res) * c.ku;
+	return A2;
+}
+
+// Build the euclidean int8 shadow: one lane per row, two passes, as
+// k_shadow_i8 (pass one also sums the squares for the norm window: a
+// euclidean table stages no norms).
+__global__ void k_shadow_l2(const float *__restrict__ cm,
+                            uint8_t *__restrict__ sh, float *__restrict__ scale,
+                            float *__restrict__ xx, float *__restrict__ res,
+                            uint64_t n, uint64_t n_pad, uint64_t sn_pad,
+                            uint32_t d) {
+	const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (r >= sn_pad)
+		return;
+	float sc = __uint_as_float(0x7FC00000u), x2 = 0.f, rs = 0.f;
+	if (r < n) {
+		pf_l2_row(cm + r, n_pad, d, sh + r, sn_pad, &sc, &x2, &rs);
+	} else { // padding row: never covered
+		for (uint32_t k = 0; k < d; k++)
+			sh[(uint64_t)k * sn_pad + r] = 128;
+	}
+	scale[r] = sc;
+	xx[r] = x2;
+	res[r] = rs;
+}
+
 // k_prefilter over the int8 shadow: 16 rows per lane from one 16-byte load
 // per feature, 8 loads in flight, one convert and one FMA per element.
 // a_i = 1 - (t_i - qbias) * inv_q * pscale_i. The block top-K and the merge
@@ -1125,7 +1355,13 @@ __global__ void k_shadow_i8(const float *__restrict__ cm,
 // The 4096-row tile feeds the select in two 2048-row halves through the
 // same 17 KB buffer k_prefilter uses. MASKED as in k_prefilter: a lane's 16
 // rows are 16 bits of one mask word, a wave's 1024 rows 16 words.
-template <bool MASKED>
+//
+// L2 (the euclidean tier): the same stream over the same codes; only the
+// side loads and the per-row finish differ. pscale holds the scales, peps
+// the xx values with the res values sn_pad floats behind them, the query's
+// PfL2Q stands behind the query at qg + d (inv_qnorm and qbias are not
+// read), and [l_i, u_i] = pf_l2_finish's [lo, up].
+template <bool MASKED, bool L2 = false>
 __global__ __launch_bounds__(THREADS) void k_prefilter_i8(
     const uint8_t *__restrict__ sh, const float *__restrict__ pscale,
     const float *__restrict__ peps, uint64_t n, uint64_t sn_pad, uint32_t d,
@@ -1197,22 +1433,41 @@ __global__ __launch_bounds__(THREADS) void k_prefilter_i8(
 #undef PF8_ACC4
 		float up[16];
 		bool ok[16];
+		PfL2Q qc = {};
+		if constexpr (L2)
+			qc = *(const PfL2Q *)(qg + d); // uniform: scalar loads
 #pragma unroll
 		for (int g = 0; g < 4; g++) {
 			const float4 s4 = *(const float4 *)(pscale + r0 + 4 * g);
 			const float4 e4 = *(const float4 *)(peps + r0 + 4 * g);
 			const float ps[4] = {s4.x, s4.y, s4.z, s4.w};
 			const float pe[4] = {e4.x, e4.y, e4.z, e4.w};
+			float pr[4] = {0.f, 0.f, 0.f, 0.f};
+			if constexpr (L2) {
+				const float4 r4 =
+				    *(const float4 *)(peps + sn_pad + r0 + 4 * g);
+				pr[0] = r4.x, pr[1] = r4.y, pr[2] = r4.z, pr[3] = r4.w;
+			}
 			float lo[4];
 #pragma unroll
 			for (int j = 0; j < 4; j++) {
 				const int c = 4 * g + j;
-				const float a =
-				    1.0f - (acc[c] - qbias) * inv_qnorm * ps[j];
-				ok[c] = (r0 + c) < row_end &&
-				        (__float_as_uint(a) & 0x7F800000u) != 0x7F800000u;
-				up[c] = ok[c] ? a + pe[j] : ninf;
-				lo[j] = ok[c] ? a - pe[j] : ninf;
+				if constexpr (L2) {
+					float lj, uj;
+					const float a = pf_l2_finish(acc[c], ps[j], pe[j], pr[j],
+					                             qc, &lj, &uj);
+					ok[c] = (r0 + c) < row_end &&
+					        (__float_as_uint(a) & 0x7F800000u) != 0x7F800000u;
+					up[c] = ok[c] ? uj : ninf;
+					lo[j] = ok[c] ? lj : ninf;
+				} else {
+					const float a =
+					    1.0f - (acc[c] - qbias) * inv_qnorm * ps[j];
+					ok[c] = (r0 + c) < row_end &&
+					        (__float_as_uint(a) & 0x7F800000u) != 0x7F800000u;
+					up[c] = ok[c] ? a + pe[j] : ninf;
+					lo[j] = ok[c] ? a - pe[j] : ninf;
+				}
 				if constexpr (MASKED) {
 					const bool allowed = (mb >> c) & 1u;
 					ok[c] = ok[c] && allowed;
@@ -1274,14 +1529,6 @@ __global__ __launch_bounds__(THREADS) void k_prefilter_i8(
 #endif
 typedef uint32_t pf6_v4 __attribute__((ext_vector_type(4)));
 typedef uint32_t pf6_v2 __attribute__((ext_vector_type(2)));
-
-// e > 0 finite, rounded up to f32.
-__host__ __device__ static inline float pf_round_up_f32(double e) {
-	float ef = (float)e;
-	if ((double)ef < e)
-		ef = __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, ef) + 1u);
-	return ef;
-}
 
 // Quantise one row for the int6 shadow (elements x[k * xstride], k < d;
 // norm = the row's staged f64 norm) and derive its bound. The one routine
@@ -1791,8 +2038,9 @@ __device__ __forceinline__ static void rows_exact(
 		                       out + c, qs, xs, ps);
 }
 
-// Exact rescore of the prefilter's candidates: rows_exact<0> over the count
-// k_pf_compact left on the device.
+// Exact rescore of the prefilter's candidates: rows_exact<METRIC> over the
+// count k_pf_compact left on the device.
+template <int METRIC>
 __global__ __launch_bounds__(64) void k_pf_rescore(
     const float *__restrict__ cm, const double *__restrict__ norms,
     const uint64_t *__restrict__ ids, uint64_t n_pad, uint32_t d,
@@ -1805,8 +2053,8 @@ __global__ __launch_bounds__(64) void k_pf_rescore(
 	const uint32_t cnt = *cand_cnt;
 	if (cnt > PF_CAND_CAP || blockIdx.x >= cnt)
 		return; // overflow: the host reruns the exact scan
-	rows_exact<0>(cm, norms, ids, n_pad, d, qg, q_norm, cand_rows, cnt, out,
-	              qs, xs, ps);
+	rows_exact<METRIC>(cm, norms, ids, n_pad, d, qg, q_norm, cand_rows, cnt,
+	                   out, qs, xs, ps);
 }
 
 // Row-list path of the filtered call: rows_exact on the
@@ -3469,31 +3717,37 @@ static void free_shadow(sdbv_ctx *ctx, Table *t) {
 // the int6 tier's H-only stream, for prefilter_grid alone: its spans are
 // whole sweeps of THREADS rows, not whole tiles, which left a fifth of the
 // device's 8 blocks per CU empty at 10M rows (profiles/prefilter_h4.md).
+// Entry 5 is the euclidean int8 tier.
 struct ShadowTier {
 	uint64_t tile;
 	uint64_t side_per_row;
 };
-static const ShadowTier SHADOW_TIERS[5] = {
-    {0, 0}, {PF_TILE, 1}, {PF8_TILE, 2}, {PF6_TILE, 3}, {THREADS, 0}};
+static const ShadowTier SHADOW_TIERS[6] = {
+    {0, 0},        {PF_TILE, 1}, {PF8_TILE, 2},
+    {PF6_TILE, 3}, {THREADS, 0}, {PF8_TILE, 3}};
 
-// bf16: 2 d bytes per row (+50 % of the f32 store); int8: d (+25 %); int6:
-// 0.75 d_pad, d_pad = d rounded up to a multiple of 32 (planes H and L).
+// bf16: 2 d bytes per row (+50 % of the f32 store); int8 and l2: d (+25 %);
+// int6: 0.75 d_pad, d_pad = d rounded up to a multiple of 32 (planes H and
+// L).
 static uint64_t shadow_code_bytes(int kind, uint32_t d, uint64_t sn_pad) {
 	switch (kind) {
 	case 1: return 2ull * d * sn_pad;
-	case 2: return (uint64_t)d * sn_pad;
+	case 2:
+	case 5: return (uint64_t)d * sn_pad;
 	default: return 24ull * ((d + 31) / 32) * sn_pad;
 	}
 }
 
-// Build the kind shadow of a staged cosine table (norms already computed, in
-// stream order), instead of any other kind the table holds. A failed
-// allocation leaves the table without a shadow and returns SDBV_ERR_OOM.
+// Build the kind shadow of a staged table (cosine: kinds 1..3, norms already
+// computed, in stream order; euclidean: kind 5), instead of any other kind
+// the table holds. A failed allocation leaves the table without a shadow and
+// returns SDBV_ERR_OOM.
 // h4 (int6 only): with the H-only side data, 8 B per row more. Staging asks
 // for it when h4_policy holds; the explicit entries build the plain shadow,
 // also in place of a staged one that carries the side data.
 static int build_shadow(sdbv_ctx *ctx, Table *t, int kind, bool h4 = false) {
-	if (t->metric != SDBV_METRIC_COSINE)
+	if (t->metric !=
+	    (kind == 5 ? SDBV_METRIC_EUCLIDEAN : SDBV_METRIC_COSINE))
 		return SDBV_ERR_UNSUPPORTED;
 	h4 = h4 && kind == 3;
 	if (t->sh.kind == kind && t->sh.h4 == h4)
@@ -3543,6 +3797,12 @@ static int build_shadow(sdbv_ctx *ctx, Table *t, int kind, bool h4 = false) {
 		                   sh.peps(), sh.xsum(), sh.peps4(), sh.xsum_h(), t->n,
 		                   t->n_pad, sn_pad, t->d);
 		break;
+	case 5: // one lane per row
+		hipLaunchKernelGGL(k_shadow_l2, dim3((uint32_t)(sn_pad / 256)),
+		                   dim3(256), 0, ctx->stream, t->cm,
+		                   (uint8_t *)sh.codes, sh.pscale(), sh.l2_xx(),
+		                   sh.l2_res(), t->n, t->n_pad, sn_pad, t->d);
+		break;
 	}
 	HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
 	HIP_CHECK(ctx, hipGetLastError());
@@ -3562,6 +3822,11 @@ static int build_shadow(sdbv_ctx *ctx, Table *t, int kind, bool h4 = false) {
 // ahead from 1 000 000 (profiles/prefilter_h4.md); never below
 // PF6_DEFAULT_MIN_ROWS.
 #define PF4_DEFAULT_MIN_ROWS 1000000ull
+// The euclidean tier's shadow at all: measured against the exact scan at
+// 200 000 (a tie), 500 000, 1 000 000 and 2 000 000 rows; 500 000 is the
+// smallest of them at which the shadow path wins by more than 10 times the
+// spread (profiles/prefilter_l2.md).
+#define PFL2_DEFAULT_MIN_ROWS 500000ull
 
 // One staging policy question: env_flag=0 answers no; otherwise the table
 // needs env_min_rows rows (default default_min). The three row counts are
@@ -3587,10 +3852,19 @@ static bool h4_policy(const Table *t) {
 	                     PF4_DEFAULT_MIN_ROWS);
 }
 
-// The shadow that scan staging builds: none off cosine or when
-// SDBV_SCAN_PREFILTER says no; else bf16 when SDBV_SCAN_PREFILTER_I8 says
-// no; else int8 when SDBV_SCAN_PREFILTER_I6 says no; else int6.
+// The shadow that scan staging builds. Euclidean: the l2 tier when
+// SDBV_SCAN_PREFILTER_L2 / SDBV_SCAN_PREFILTER_L2_MIN_ROWS say yes, a pair of
+// its own (the cosine variables give a euclidean table nothing). Cosine: none
+// when SDBV_SCAN_PREFILTER says no; else bf16 when SDBV_SCAN_PREFILTER_I8
+// says no; else int8 when SDBV_SCAN_PREFILTER_I6 says no; else int6. Any
+// other metric: none.
 static int staged_shadow_kind(const Table *t) {
+	if (t->metric == SDBV_METRIC_EUCLIDEAN)
+		return shadow_policy(t, "SDBV_SCAN_PREFILTER_L2",
+		                     "SDBV_SCAN_PREFILTER_L2_MIN_ROWS",
+		                     PFL2_DEFAULT_MIN_ROWS)
+		           ? 5
+		           : 0;
 	if (t->metric != SDBV_METRIC_COSINE ||
 	    !shadow_policy(t, "SDBV_SCAN_PREFILTER", "SDBV_SCAN_PREFILTER_MIN_ROWS",
 	                   PF_DEFAULT_MIN_ROWS))
@@ -3728,6 +4002,23 @@ int sdbv_table_set_prefilter_i6(sdbv_ctx *ctx, uint64_t table) {
 	return set_shadow_kind(ctx, table, 3);
 }
 
+// The euclidean tier's entry: the three above keep refusing a euclidean
+// table, this one refuses every other metric.
+int sdbv_table_set_prefilter_l2(sdbv_ctx *ctx, uint64_t table, int on) {
+	if (on)
+		return set_shadow_kind(ctx, table, 5);
+	std::lock_guard<std::mutex> lk(ctx->mu);
+	auto it = ctx->tables.find(table);
+	if (it == ctx->tables.end())
+		return SDBV_ERR_NO_TABLE;
+	Table *t = &it->second;
+	if (t->metric != SDBV_METRIC_EUCLIDEAN)
+		return SDBV_ERR_UNSUPPORTED;
+	if (t->sh.kind)
+		free_shadow(ctx, t);
+	return SDBV_OK;
+}
+
 float sdbv_prefilter_eps(uint32_t d) { return pf_eps(d); }
 
 // Proven bound on |key - E| of the batch path: key is the
@@ -3757,6 +4048,39 @@ int sdbv_prefilter_i8_row(const float *x, uint32_t d, double norm,
 	pf_i8_row(x, 1, d, norm, stored, 1, scale, &pscale, eps);
 	for (uint32_t k = 0; k < d; k++)
 		codes[k] = (int8_t)((int)stored[k] - 128);
+	return SDBV_OK;
+}
+
+int sdbv_prefilter_l2_row(const float *x, uint32_t d, int8_t *codes,
+                          float *scale, float *xx, float *res) {
+	if (!x || !codes || !scale || !xx || !res || d == 0 || d > MAX_D)
+		return SDBV_ERR_BAD_ARG;
+	uint8_t stored[MAX_D];
+	pf_l2_row(x, 1, d, stored, 1, scale, xx, res);
+	for (uint32_t k = 0; k < d; k++)
+		codes[k] = (int8_t)((int)stored[k] - 128);
+	return SDBV_OK;
+}
+
+// One row of k_prefilter_i8<., true>: the same FMA chain over the stored
+// bytes, the same pf_l2_finish. *lo = -inf and *up = +inf for a row without
+// a bound (scale NaN); SDBV_ERR_UNSUPPORTED for a query outside the window.
+int sdbv_prefilter_l2_interval(const float *q, uint32_t d, const int8_t *codes,
+                               float scale, float xx, float res, float *lo,
+                               float *up) {
+	if (!q || !codes || !lo || !up || d == 0 || d > MAX_D)
+		return SDBV_ERR_BAD_ARG;
+	PfL2Q qc;
+	if (!pf_l2_query(q, d, &qc))
+		return SDBV_ERR_UNSUPPORTED;
+	float t = 0.f;
+	for (uint32_t k = 0; k < d; k++)
+		t = fmaf((float)((int)codes[k] + 128), q[k], t);
+	const float a2 = pf_l2_finish(t, scale, xx, res, qc, lo, up);
+	if ((__builtin_bit_cast(uint32_t, a2) & 0x7F800000u) == 0x7F800000u) {
+		*lo = -__builtin_inff();
+		*up = __builtin_inff();
+	}
 	return SDBV_OK;
 }
 
@@ -4073,8 +4397,8 @@ static int knn_large_k(sdbv_ctx *ctx, Table &t, const float *q, uint32_t d,
 	return SDBV_OK;
 }
 
-// Row-span grid of the prefilter sweep of shadow tier kind (1..3; 4 = the
-// int6 tier's H-only stream, unmasked only): contiguous
+// Row-span grid of the prefilter sweep of shadow tier kind (1..3 and 5; 4 =
+// the int6 tier's H-only stream, unmasked only): contiguous
 // spans of the tier's tiles, sized so that the whole grid is resident at once
 // (one round, every block the same span). A grid of a few more blocks than
 // the chip holds runs a second, mostly empty round with too few bytes in
@@ -4101,6 +4425,10 @@ static uint64_t prefilter_grid(sdbv_ctx *ctx, uint64_t n, int kind,
 			break;
 		case 4:
 			kernel = (const void *)k_prefilter_i6<false, true>;
+			break;
+		case 5:
+			kernel = masked ? (const void *)k_prefilter_i8<true, true>
+			                : (const void *)k_prefilter_i8<false, true>;
 			break;
 		}
 		hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(
@@ -4137,12 +4465,19 @@ static inline int shadow_kind(const Table &t) { return t.sh.kind; }
 // Upload the query for a call that may take the prefilter of tier kind (0:
 // none, the plain query): the int6 tier's digit words ride behind the query
 // in the same copy and *q6 receives its kernel operands; *qbias receives the
-// int8 tier's bias term 128 * sum q_k, one f64 sum rounded once.
+// int8 tier's bias term 128 * sum q_k, one f64 sum rounded once. The l2
+// tier's PfL2Q (the caller's, from pf_l2_query) rides behind the query too.
 static int stage_query_pf(sdbv_ctx *ctx, const float *q, uint32_t d,
-                          double q_norm, int kind, PfQ6 *q6, float *qbias) {
+                          double q_norm, int kind, PfQ6 *q6, float *qbias,
+                          const PfL2Q *l2 = nullptr) {
 	size_t q_bytes = d * sizeof(float);
 	*qbias = 0.f;
-	if (kind == 3) {
+	if (kind == 5) {
+		// fits: the buffers hold at least PF6_QWORDS dwords behind the query
+		static_assert(sizeof(PfL2Q) <= PF6_QWORDS * sizeof(uint32_t), "");
+		std::memcpy(ctx->q_pin + d, l2, sizeof(PfL2Q));
+		q_bytes += sizeof(PfL2Q);
+	} else if (kind == 3) {
 		const uint32_t G = (d + 31) / 32;
 		float sq, rho;
 		uint32_t qs;
@@ -4183,8 +4518,8 @@ static int ensure_prefilter_scratch(sdbv_ctx *ctx, uint64_t sn_pad) {
 	return SDBV_OK;
 }
 
-// The prefilter path of sdbv_knn_bruteforce (cosine, k <= MAX_K, table with
-// a shadow, query inside the norm window; q already in ctx->q_dev and the
+// The prefilter path of sdbv_knn_bruteforce (k <= MAX_K, table with a
+// shadow, query inside the tier's window; q already in ctx->q_dev and the
 // query scratch sized for prefilter_grid). host_out[0..k) receives the
 // exact top-k, *ncand the candidate count; *ncand > PF_CAND_CAP means the
 // list overflowed and host_out is void: the caller runs the exact scan.
@@ -4212,19 +4547,22 @@ static int knn_prefilter(sdbv_ctx *ctx, Table &t, uint32_t k, double q_norm,
 	const float inv_q = (float)(1.0 / q_norm);
 
 	HIP_CHECK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-#define LAUNCH_PF(KERNEL, ...)                                                 \
+// KT / KF: the kernel's MASKED and unmasked instantiations
+#define LAUNCH_PF2(KT, KF, ...)                                                \
 	do {                                                                       \
 		if (mask)                                                              \
-			hipLaunchKernelGGL(KERNEL<true>, dim3((uint32_t)nblocks),          \
-			                   dim3(THREADS), 0, ctx->stream, __VA_ARGS__,     \
-			                   rows_per_block, ctx->pf_scores,                 \
-			                   (Cand *)ctx->block_out, cand_cnt, mask);        \
+			hipLaunchKernelGGL(KT, dim3((uint32_t)nblocks), dim3(THREADS), 0,  \
+			                   ctx->stream, __VA_ARGS__, rows_per_block,       \
+			                   ctx->pf_scores, (Cand *)ctx->block_out,         \
+			                   cand_cnt, mask);                                \
 		else                                                                   \
-			hipLaunchKernelGGL(KERNEL<false>, dim3((uint32_t)nblocks),         \
-			                   dim3(THREADS), 0, ctx->stream, __VA_ARGS__,     \
-			                   rows_per_block, ctx->pf_scores,                 \
-			                   (Cand *)ctx->block_out, cand_cnt, mask);        \
+			hipLaunchKernelGGL(KF, dim3((uint32_t)nblocks), dim3(THREADS), 0,  \
+			                   ctx->stream, __VA_ARGS__, rows_per_block,       \
+			                   ctx->pf_scores, (Cand *)ctx->block_out,         \
+			                   cand_cnt, mask);                                \
 	} while (0)
+#define LAUNCH_PF(KERNEL, ...)                                                 \
+	LAUNCH_PF2(KERNEL<true>, KERNEL<false>, __VA_ARGS__)
 	switch (kind) {
 	case 1:
 		LAUNCH_PF(k_prefilter, (const uint16_t *)sh.codes, sh.pinv(), t.n,
@@ -4241,7 +4579,13 @@ static int knn_prefilter(sdbv_ctx *ctx, Table &t, uint32_t k, double q_norm,
 		          (const uint32_t *)(ctx->q_dev + t.d), q6.qscale, q6.qeps,
 		          q6.bias, k);
 		break;
+	case 5: // the int8 stream with the euclidean finish: inv_q is not read
+		LAUNCH_PF2((k_prefilter_i8<true, true>), (k_prefilter_i8<false, true>),
+		           (const uint8_t *)sh.codes, sh.pscale(), sh.l2_xx(), t.n,
+		           sh.sn_pad, t.d, ctx->q_dev, 0.f, qbias, k);
+		break;
 	}
+#undef LAUNCH_PF2
 #undef LAUNCH_PF
 	HIP_CHECK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
 	// K smallest approximate distances (int8, int6: upper bounds) ->
@@ -4258,13 +4602,19 @@ static int knn_prefilter(sdbv_ctx *ctx, Table &t, uint32_t k, double q_norm,
 		hipLaunchKernelGGL(k_pf_compact, dim3((uint32_t)nb), dim3(THREADS), 0,
 		                   ctx->stream, ctx->pf_scores, t.n,
 		                   (const Cand *)ctx->final_out, k,
-		                   // per-row bounds (int8, int6): no window on top
+		                   // per-row bounds (int8, int6, l2): no window on top
 		                   kind == 1 ? pf_eps(t.d) : 0.0f, cand_cnt,
 		                   ctx->pf_rows);
-		hipLaunchKernelGGL(k_pf_rescore, dim3(PF_RESCORE_BLOCKS), dim3(64), 0,
-		                   ctx->stream, t.cm, t.norms, t.ids_dev, t.n_pad,
-		                   t.d, ctx->q_dev, q_norm, cand_cnt, ctx->pf_rows,
-		                   (Cand *)ctx->pf_cands);
+		if (kind == 5)
+			hipLaunchKernelGGL(k_pf_rescore<1>, dim3(PF_RESCORE_BLOCKS),
+			                   dim3(64), 0, ctx->stream, t.cm, t.norms,
+			                   t.ids_dev, t.n_pad, t.d, ctx->q_dev, q_norm,
+			                   cand_cnt, ctx->pf_rows, (Cand *)ctx->pf_cands);
+		else
+			hipLaunchKernelGGL(k_pf_rescore<0>, dim3(PF_RESCORE_BLOCKS),
+			                   dim3(64), 0, ctx->stream, t.cm, t.norms,
+			                   t.ids_dev, t.n_pad, t.d, ctx->q_dev, q_norm,
+			                   cand_cnt, ctx->pf_rows, (Cand *)ctx->pf_cands);
 	}
 	HIP_CHECK(ctx, hipEventRecord(ctx->ev3, ctx->stream));
 	hipLaunchKernelGGL(k_pf_final, dim3(1), dim3(THREADS), 0, ctx->stream,
@@ -4368,8 +4718,8 @@ static int knn_prefilter_h4(sdbv_ctx *ctx, Table &t, uint32_t k, double q_norm,
 		                   q6.qscale, q6.qeps, q6.bias, thr, k, list_cap,
 		                   cand_cnt + 1, ctx->pf4_list, cand_cnt,
 		                   ctx->pf_rows);
-		hipLaunchKernelGGL(k_pf_rescore, dim3(PF_RESCORE_BLOCKS), dim3(64), 0,
-		                   ctx->stream, t.cm, t.norms, t.ids_dev, t.n_pad,
+		hipLaunchKernelGGL(k_pf_rescore<0>, dim3(PF_RESCORE_BLOCKS), dim3(64),
+		                   0, ctx->stream, t.cm, t.norms, t.ids_dev, t.n_pad,
 		                   t.d, ctx->q_dev, q_norm, cand_cnt, ctx->pf_rows,
 		                   (Cand *)ctx->pf_cands);
 	}
@@ -4460,15 +4810,19 @@ int sdbv_knn_bruteforce(sdbv_ctx *ctx, uint64_t table, const float *q,
 	if (rc != SDBV_OK)
 		return rc;
 	double q_norm = sqrt((double)h_sumsq_f32(q, d));
-	// Prefilter path: a shadowed cosine table and a query whose norm lies in
-	// the window the bound is proven for (a non-finite element makes the
-	// norm non-finite). Everything else, and a query whose candidate list
-	// overflowed, takes the exact scan; results never depend on the choice.
+	// Prefilter path: a shadowed table and a query whose norm lies in the
+	// window the bound is proven for (a non-finite element makes the norm
+	// non-finite); the l2 tier's window is pf_l2_query's and holds the zero
+	// query. Everything else, and a query whose candidate list overflowed,
+	// takes the exact scan; results never depend on the choice.
+	PfL2Q l2q;
 	const bool use_pf =
-	    kind != 0 && q_norm >= PF_NORM_MIN && q_norm <= PF_NORM_MAX;
+	    kind == 5 ? pf_l2_query(q, d, &l2q)
+	              : kind != 0 && q_norm >= PF_NORM_MIN && q_norm <= PF_NORM_MAX;
 	PfQ6 q6;
 	float qbias = 0.f;
-	rc = stage_query_pf(ctx, q, d, q_norm, use_pf ? kind : 0, &q6, &qbias);
+	rc = stage_query_pf(ctx, q, d, q_norm, use_pf ? kind : 0, &q6, &qbias,
+	                    &l2q);
 	if (rc != SDBV_OK)
 		return rc;
 
@@ -4496,8 +4850,10 @@ int sdbv_knn_bruteforce(sdbv_ctx *ctx, uint64_t table, const float *q,
 		if (rc != SDBV_OK)
 			return rc;
 		ctx->stats.last_prefilter_candidates = ncand;
+		// 1..6 by cosine tier; the l2 tier's 17 / 18 lie behind the filtered
+		// call's and the two-stage path's numbers
 		ctx->stats.last_scan_path = (ncand <= PF_CAND_CAP ? 1u : 2u) +
-		                            2u * (uint32_t)(kind - 1);
+		                            (kind == 5 ? 16u : 2u * (uint32_t)(kind - 1));
 	}
 	if (!(ctx->stats.last_scan_path & 1u)) {
 		rc = knn_exact_scan(ctx, t, k, q_norm, nblocks, rows_per_block,
@@ -4702,13 +5058,16 @@ int sdbv_knn_bruteforce_filtered(sdbv_ctx *ctx, uint64_t table, const float *q,
 	const bool by_list = count <= list_max;
 	double q_norm = sqrt((double)h_sumsq_f32(q, d));
 	// Shadow path: more allowed rows than the list serves,
-	// a shadowed (hence cosine) table the policy admits, and a query inside
-	// the norm window the bounds are proven for. Everything else, and a call
-	// whose candidate list overflowed, takes the path it took before;
-	// results never depend on the choice.
+	// a shadowed table the policy admits, and a query inside the window the
+	// tier's bounds are proven for. Everything else, and a call whose
+	// candidate list overflowed, takes the path it took before; results
+	// never depend on the choice.
 	const int kind = shadow_kind(t);
-	const bool use_pf = !by_list && kind != 0 && q_norm >= PF_NORM_MIN &&
-	                    q_norm <= PF_NORM_MAX && filter_prefilter_policy(t);
+	PfL2Q l2q;
+	const bool use_pf =
+	    !by_list && kind != 0 && filter_prefilter_policy(t) &&
+	    (kind == 5 ? pf_l2_query(q, d, &l2q)
+	               : q_norm >= PF_NORM_MIN && q_norm <= PF_NORM_MAX);
 	// the masked scan runs on k_scan's grid; block_out serves whichever of
 	// the two grids runs, since an overflow reruns the masked scan
 	uint64_t rows_per_block = 0;
@@ -4722,7 +5081,8 @@ int sdbv_knn_bruteforce_filtered(sdbv_ctx *ctx, uint64_t table, const float *q,
 		return rc;
 	PfQ6 q6;
 	float qbias = 0.f;
-	rc = stage_query_pf(ctx, q, d, q_norm, use_pf ? kind : 0, &q6, &qbias);
+	rc = stage_query_pf(ctx, q, d, q_norm, use_pf ? kind : 0, &q6, &qbias,
+	                    &l2q);
 	if (rc != SDBV_OK)
 		return rc;
 	if (!by_list) {
@@ -4739,7 +5099,7 @@ int sdbv_knn_bruteforce_filtered(sdbv_ctx *ctx, uint64_t table, const float *q,
 			return rc;
 		ctx->stats.last_prefilter_candidates = ncand;
 		ctx->stats.last_scan_path = (ncand <= PF_CAND_CAP ? 9u : 10u) +
-		                            2u * (uint32_t)(kind - 1);
+		                            (kind == 5 ? 10u : 2u * (uint32_t)(kind - 1));
 	}
 	if (!(ctx->stats.last_scan_path & 1u)) {
 		// no shadow pass, or one that overflowed: the mask is on the device
