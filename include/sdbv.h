@@ -62,7 +62,9 @@ enum {
 /* Distance metric — mirrors catalog::Distance
  * (surrealdb/core/src/catalog/schema/index.rs:250-284), all 8 variants on
  * the GPU scan. COSINE/EUCLIDEAN run the LDS-tiled k_scan (the headline
- * path); the others run an all-distances kernel + exact top-k selection
+ * path); the others run an all-distances kernel + exact top-k selection,
+ * on the device for tables the policy admits and k <= 65536, on the host
+ * otherwise (see sdbv_knn_bruteforce; the same at any metric for k > 64)
  * (each restating the reference's F32 chain, vector.rs:206-451 —
  * including jaccard's bit-pattern sets :317-340 and the F32 |I|/|U|
  * asymmetry, and pearson's similarity-as-distance :413-440). MINKOWSKI
@@ -108,7 +110,16 @@ typedef struct sdbv_stats {
 	                            prefilter, 18 = that overflowed, then exact
 	                            scan; sdbv_knn_bruteforce_filtered: 19 = l2
 	                            prefilter under the bitmap, 20 = that
-	                            overflowed, then masked scan */
+	                            overflowed, then masked scan. The
+	                            all-distances route with the top-K selected
+	                            on the device: 21 = sdbv_knn_bruteforce (and
+	                            the per-query calls of sdbv_knn_batch on a
+	                            non-GEMM metric), 22 = under the bitmap of
+	                            sdbv_knn_bruteforce_filtered; with the host
+	                            selection the route stays 0. On 21 / 22
+	                            last_scan_kernel_ms is the all-distances
+	                            launch, last_merge_kernel_ms the select
+	                            passes and the emit */
 	uint64_t last_filter_rows; /* allowed rows of the last filtered call (for
 	                              such a call last_rows_scanned is the same
 	                              count) */
@@ -300,9 +311,21 @@ void sdbv_gen_f32(uint64_t seed, uint64_t row0, uint64_t nrows, uint32_t d,
  * Results sorted ascending by (distance f64-total_cmp, id).
  * Distances follow Distance::calculate F32 semantics (vector.rs:244-249 /
  * 282-283): f32 accumulation per the restated ndarray contract, f64 finish.
- * k <= 64 runs fully on-device (block-local exact top-K); larger k
- * (the reference accepts any) takes one all-distances launch + exact host
- * selection — same ordering contract, costing an n-f64 transfer.
+ * COSINE/EUCLIDEAN with k <= 64 run fully on-device (block-local exact
+ * top-K). Larger k (the reference accepts any) and the six other metrics
+ * take one all-distances launch into context-owned scratch, then an exact
+ * selection under the same ordering contract:
+ *  - on the device (last_scan_path 21) when k <= 65536, the table has fewer
+ *    than 2^32 rows and at least SDBV_SELECT_DEVICE_MIN_ROWS of them
+ *    (environment, read at each call, default 65536) and SDBV_SELECT_DEVICE
+ *    is not 0 (read at each call): an MSB-first radix select over (distance
+ *    total_cmp key, row), 8 bits per pass, finds the k-th smallest pair; the
+ *    rows at or below it, k of them exactly, come back and the host sorts
+ *    them. The pairs are distinct, so the set is unique and the result is
+ *    the host selection's in every bit. A count other than min(k, n) is
+ *    SDBV_ERR_HIP, never a shorter result;
+ *  - on the host otherwise (last_scan_path 0), costing an n-f64 and an n-id
+ *    transfer per query.
  * *out_n = min(k, n).
  *
  * On a cosine table with a prefilter shadow (k <= 64, finite query with a
@@ -376,8 +399,12 @@ int sdbv_knn_bruteforce(sdbv_ctx *, uint64_t table, const float *q, uint32_t d,
  * bitmap as a second validity test, which skips every 256-row segment
  * without an allowed row (last_scan_path 7). The shadow is only read: an
  * unfiltered call before or after is not disturbed. Other metrics and
- * larger k take the all-distances launch with a host selection that skips
- * the rows not allowed (last_scan_path 0). */
+ * larger k take the all-distances launch over every row, then a selection
+ * that skips the rows not allowed: the device select of sdbv_knn_bruteforce
+ * under the bitmap (last_scan_path 22) when k <= 65536 and
+ * SDBV_SELECT_DEVICE / SDBV_SELECT_DEVICE_MIN_ROWS admit the table (the
+ * minimum counts the table's rows, not the allowed ones), the host selection
+ * otherwise (last_scan_path 0). */
 int sdbv_knn_bruteforce_filtered(sdbv_ctx *, uint64_t table, const float *q,
                                  uint32_t d, uint32_t k,
                                  const uint64_t *allow, uint64_t allow_words,
@@ -389,6 +416,15 @@ int sdbv_knn_bruteforce_filtered(sdbv_ctx *, uint64_t table, const float *q,
  * past n are ignored. */
 uint64_t sdbv_filter_rows(const uint64_t *allow, uint64_t allow_words,
                           uint64_t n, uint32_t *out_rows, uint64_t cap);
+/* Host-only: the digit walk of the device select on host histograms, sharing
+ * its per-pass step with the kernels. Of the n < 2^32 f64 values in dists,
+ * restricted to the rows `allow` admits (NULL = all; else ceil(n / 64) words,
+ * bits at or past n ignored), writes the rows of the min(k, rows considered)
+ * smallest to out_rows in result order — ascending f64 total order (-NaN,
+ * -inf, ..., -0, +0, ..., +inf, +NaN), ties by ascending row — and their
+ * number to *out_n. SDBV_OK, or SDBV_ERR_BAD_ARG. */
+int sdbv_select_topk(const double *dists, uint64_t n, const uint64_t *allow,
+                     uint32_t k, uint32_t *out_rows, uint32_t *out_n);
 
 /* Batched-query brute-force: Q is b x d row-major; out_ids/out_dists are
  * b x k row-major, a query with fewer than k rows padded with id ~0 and

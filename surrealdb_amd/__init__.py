@@ -51,7 +51,9 @@ class _Stats(ctypes.Structure):
     overflow, then exact scan); 7 masked scan, 8 row list, 9..14 the cosine
     tiers under a filter; 15 / 16 the two-stage int6 path; 17 / 18 the
     euclidean (l2) prefilter and its overflow, 19 / 20 the same under a
-    filter. last_prefilter_candidates: rows passed to the exact rescore."""
+    filter; 21 / 22 the all-distances route with the device select, plain
+    and under a filter (0 with the host selection).
+    last_prefilter_candidates: rows passed to the exact rescore."""
     _fields_ = [
         ("last_scan_kernel_ms", ctypes.c_double),
         ("last_merge_kernel_ms", ctypes.c_double),
@@ -132,6 +134,7 @@ def lib():
                                                u64, u64p, f64p, u32p]
     L.sdbv_filter_rows.restype = u64
     L.sdbv_filter_rows.argtypes = [u64p, u64, u64, u32p, u64]
+    L.sdbv_select_topk.argtypes = [f64p, u64, u64p, u32, u32p, u32p]
     L.sdbv_all_distances.argtypes = [vp, u64, f32p, u32, f64p]
     L.sdbv_gather_distance.argtypes = [vp, u64, u32p, u32, f32p, u32, f64p]
     L.sdbv_knn_batch.argtypes = [vp, u64, f32p, u32, u32, u32, u64p, f64p]
@@ -307,6 +310,14 @@ class Context:
             self._ptr, table, int(bool(on))), "sdbv_table_set_prefilter_l2")
 
     def knn_bruteforce(self, table, q, k):
+        """Exact top-k of a staged table: (ids, dists), ascending (distance
+        total order, id). Cosine / euclidean with k <= 64 run the scan or
+        the table's prefilter tier. Every other metric, and any k > 64,
+        takes the all-distances launch and then selects the top-k on the
+        device (stats last_scan_path 21: k <= 65536, a table of at least
+        SDBV_SELECT_DEVICE_MIN_ROWS rows, default 65536, unless
+        SDBV_SELECT_DEVICE=0; both read at each call) or on the host
+        (last_scan_path 0). The choice never changes a result."""
         import numpy as np
         q = np.ascontiguousarray(q, dtype=np.float32)
         ids = np.empty(k, dtype=np.uint64)
@@ -334,7 +345,9 @@ class Context:
         SDBV_FILTER_PREFILTER=0 (9 / 11 / 13 by tier, the even number after
         it when the candidate list overflowed), and likewise the l2 shadow
         of a euclidean table (19 / 20); the masked exact scan otherwise
-        (7)."""
+        (7). Other metrics and k > 64 take the all-distances launch, then
+        the device select under the bitmap (22) by the rule of
+        knn_bruteforce, or the host selection (0)."""
         import numpy as np
         q = np.ascontiguousarray(q, dtype=np.float32)
         n = self.table_rows(table)
@@ -441,6 +454,29 @@ def filter_rows(allow, n, cap=None):
         words.ctypes.data_as(u64p), words.size, n,
         rows.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), int(cap))
     return int(count), rows[:min(int(count), int(cap))]
+
+
+def select_topk(dists, k, allow=None):
+    """Host-only twin of the device select: the rows of the min(k, rows
+    considered) smallest of the f64 array `dists`, in result order (f64
+    total order, ties by ascending row), as a uint32 array. `allow` as for
+    knn_bruteforce_filtered (None = every row). Runs the device select's
+    digit walk on host histograms."""
+    import numpy as np
+    dists = np.ascontiguousarray(dists, dtype=np.float64)
+    n = dists.size
+    words = None if allow is None else _allow_words(allow, n)
+    rows = np.empty(max(min(int(k), n), 1), dtype=np.uint32)
+    out_n = ctypes.c_uint32(0)
+    rc = lib().sdbv_select_topk(
+        dists.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), n,
+        None if words is None
+        else words.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)),
+        int(k), rows.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
+        ctypes.byref(out_n))
+    if rc != 0:
+        raise SdbvError(f"sdbv_select_topk failed ({rc})")
+    return rows[:out_n.value]
 
 
 def prefilter_eps(d):

@@ -197,6 +197,14 @@ struct sdbv_ctx {
 	uint32_t *flt_rows = nullptr;     // [PF_CAND_CAP] allowed rows, device
 	uint32_t *flt_rows_pin = nullptr; // pinned: the host builds the list here
 	void *flt_cands = nullptr;        // [PF_CAND_CAP] Cand of the listed rows
+	// device select of the all-distances route, grown on
+	// demand
+	double *sel_dists = nullptr; // [n] the all-distances buffer
+	uint64_t sel_dists_cap = 0;  // bytes
+	void *sel_dev = nullptr;     // SelDev, then [k_eff] Cand
+	uint64_t sel_dev_cap = 0;    // bytes
+	void *sel_pin = nullptr;     // pinned: SelHead, then [k_eff] Cand
+	uint64_t sel_pin_cap = 0;    // bytes
 };
 
 struct Cand {
@@ -3582,6 +3590,259 @@ static void free_table(Table &t) {
 }
 
 // ---------------------------------------------------------------------------
+// Device select of the all-distances route
+// ---------------------------------------------------------------------------
+// The k_eff smallest rows of the all-distances buffer under knn_large_k's own
+// order, ascending (total_key(dist), row), found on the device: an MSB-first
+// radix select over the 96-bit composite (64-bit total-order key, 32-bit
+// row), 8 bits per pass. Composites are distinct, so the walk ends on one
+// threshold and the selected set is unique. The kernel boundary is the only
+// synchronisation: pass p reads what launches before it wrote, never what a
+// block of its own launch writes.
+
+#define SEL_MAX_K 65536u /* larger k keeps the host selection */
+#define SEL_PASSES 12    /* 8 key digits, then 4 row digits */
+#define SEL_CHUNKS 4     /* 256-row chunks a block loads before counting */
+#define SEL_MAX_BLOCKS 2048
+// Smallest table the device select serves by default
+// (SDBV_SELECT_DEVICE_MIN_ROWS). Measured at 16384, 65536, 262144 and
+// 1048576 rows x 768 on manhattan K=10 and cosine K=100: the smallest of them
+// at which the device route's p50 last_total_ms beats the host route's by
+// more than 10 times the host route's p50-to-p95 gap on both, in both runs
+// (profiles/select_device.md; at 16384 the device route is ahead as well,
+// but one cosine run missed that margin). Never below 16384.
+#define SEL_DEFAULT_MIN_ROWS 65536ull
+
+// The walk's state on entering a pass: the digits chosen so far in the high
+// bits of (key, row), zeros below; need = how many of the rows under this
+// prefix belong to the result. done: every row under the prefix belongs to
+// it; the bits below the prefix are then all ones, (key, row) is the final
+// threshold and later passes have nothing to count.
+struct SelState {
+	uint64_t key;
+	uint32_t row;
+	uint32_t need;
+	uint32_t done;
+	uint32_t pad;
+};
+
+struct SelHead {
+	uint32_t count; // slots the emit handed out
+	uint32_t pad;
+};
+
+// Device scratch of one select, zeroed by one memset before the first pass;
+// the k_eff result slots follow it, so head and results come back in one copy.
+struct SelDev {
+	uint32_t hist[SEL_PASSES][256];
+	SelState st[SEL_PASSES]; // st[p]: state on entering pass p
+	SelHead head;
+};
+static_assert(offsetof(SelDev, head) + sizeof(SelHead) == sizeof(SelDev) &&
+                  sizeof(SelDev) % alignof(Cand) == 0,
+              "result slots follow the head directly");
+
+// d_total_key for host and device.
+__host__ __device__ static inline uint64_t sel_total_key(double x) {
+	uint64_t bits;
+	__builtin_memcpy(&bits, &x, 8);
+	return (bits >> 63) ? ~bits : (bits | 0x8000000000000000ULL);
+}
+
+// The digit of pass p: passes 0..7 walk the key from its top byte, 8..11 the
+// row from its top byte.
+__host__ __device__ static inline uint32_t sel_digit(uint64_t key, uint32_t row,
+                                                     int pass) {
+	return pass < 8 ? (uint32_t)(key >> (56 - 8 * pass)) & 255u
+	                : (row >> (24 - 8 * (pass - 8))) & 255u;
+}
+
+// Whether the digits above pass p's equal the prefix in s.
+__host__ __device__ static inline bool sel_match(uint64_t key, uint32_t row,
+                                                 const SelState &s, int pass) {
+	if (pass == 0)
+		return true;
+	if (pass < 8)
+		return (key >> (64 - 8 * pass)) == (s.key >> (64 - 8 * pass));
+	if (key != s.key)
+		return false;
+	if (pass == 8)
+		return true;
+	const int sh = 32 - 8 * (pass - 8);
+	return (row >> sh) == (s.row >> sh);
+}
+
+// Set the digits of passes from..11 to all ones.
+__host__ __device__ static inline void sel_fill(SelState *s, int from) {
+	if (from < 8) {
+		const int bits = 64 - 8 * from;
+		s->key |= bits == 64 ? ~0ULL : (1ULL << bits) - 1;
+		s->row = ~0u;
+	} else if (from < SEL_PASSES) {
+		const int bits = 32 - 8 * (from - 8);
+		s->row |= bits == 32 ? ~0u : (1u << bits) - 1;
+	}
+}
+
+// One step of the walk, shared by the kernels and sdbv_select_topk: hist is
+// pass p's histogram over the rows under s's prefix. The digit chosen is the
+// first whose running count reaches need; the rows of smaller digits all
+// belong to the result and leave need. When the chosen bin holds exactly the
+// rows still needed the walk is done. A histogram that cannot reach need (the
+// caller's k_eff exceeds the rows it counted) selects everything under the
+// prefix; the caller's slot count then shows the mismatch. No early exit from
+// the loop: the loads batch.
+__host__ __device__ static inline void sel_step(const uint32_t *hist, int pass,
+                                                SelState *s) {
+	if (s->done)
+		return;
+	uint32_t digit = 256, before = 0, acc = 0;
+	for (uint32_t b = 0; b < 256; b++) {
+		const uint32_t c = hist[b];
+		const bool hit = digit == 256 && c != 0 && acc + c >= s->need;
+		digit = hit ? b : digit;
+		before = hit ? acc : before;
+		acc += c;
+	}
+	if (digit == 256) {
+		sel_fill(s, pass);
+		s->done = 1;
+		return;
+	}
+	s->need -= before;
+	if (pass < 8)
+		s->key |= (uint64_t)digit << (56 - 8 * pass);
+	else
+		s->row |= digit << (24 - 8 * (pass - 8));
+	if (hist[digit] == s->need) {
+		sel_fill(s, pass + 1);
+		s->done = 1;
+	}
+}
+
+// (key, row) at or below the final threshold.
+__host__ __device__ static inline bool sel_below(uint64_t key, uint32_t row,
+                                                 const SelState &s) {
+	return key < s.key || (key == s.key && row <= s.row);
+}
+
+// Head of every select kernel: the state on entering `pass` (SEL_PASSES = the
+// emit), stepped by one thread from the previous pass's finished histogram
+// and state; every block computes the same, block 0 records it for the next
+// launch. h is the block's 256-bin LDS histogram, left zeroed.
+__device__ static inline SelState sel_enter(SelDev *dev, int pass,
+                                            uint32_t k_eff, uint32_t *h,
+                                            SelState *st) {
+	const uint32_t tid = threadIdx.x;
+	if (pass == 0) {
+		if (tid == 0)
+			*st = SelState{0, 0, k_eff, 0, 0};
+	} else {
+		h[tid] = dev->hist[pass - 1][tid];
+		__syncthreads();
+		if (tid == 0) {
+			SelState s = dev->st[pass - 1];
+			sel_step(h, pass - 1, &s);
+			*st = s;
+		}
+	}
+	__syncthreads();
+	if (tid == 0 && blockIdx.x == 0 && pass < SEL_PASSES)
+		dev->st[pass] = *st;
+	h[tid] = 0;
+	__syncthreads();
+	return *st;
+}
+
+// One histogram pass: count pass's digit over the rows below n that the
+// bitmap allows and whose higher digits equal the prefix. Per-block LDS
+// histogram, flushed once. On a hamming or jaccard table nearly all rows
+// share their upper digits, so a wave first tests whether its active lanes
+// carry one digit and then adds their number with one LDS atomic.
+template <bool MASKED>
+__global__ void __launch_bounds__(THREADS)
+k_sel_hist(const double *__restrict__ dists, uint64_t n,
+           const uint64_t *__restrict__ mask, SelDev *dev, int pass,
+           uint32_t k_eff) {
+	__shared__ uint32_t h[256];
+	__shared__ SelState st;
+	const SelState s = sel_enter(dev, pass, k_eff, h, &st);
+	if (s.done)
+		return;
+	const uint32_t tid = threadIdx.x, lane = tid & 63u;
+	const uint64_t span = (uint64_t)THREADS * SEL_CHUNKS;
+	for (uint64_t base = (uint64_t)blockIdx.x * span; base < n;
+	     base += (uint64_t)gridDim.x * span) {
+		double v[SEL_CHUNKS];
+#pragma unroll
+		for (int u = 0; u < SEL_CHUNKS; u++) {
+			const uint64_t r = base + (uint64_t)u * THREADS + tid;
+			v[u] = r < n ? dists[r] : 0.0;
+		}
+#pragma unroll
+		for (int u = 0; u < SEL_CHUNKS; u++) {
+			const uint64_t r = base + (uint64_t)u * THREADS + tid;
+			bool act = r < n;
+			if (MASKED && act)
+				act = (mask[r >> 6] >> (r & 63)) & 1ULL;
+			const uint64_t key = sel_total_key(v[u]);
+			act = act && sel_match(key, (uint32_t)r, s, pass);
+			const uint32_t dg = sel_digit(key, (uint32_t)r, pass);
+			const unsigned long long m = __ballot(act);
+			if (m) {
+				const int first = __ffsll(m) - 1;
+				const uint32_t d0 = (uint32_t)__shfl((int)dg, first);
+				if (__ballot(act && dg == d0) == m) {
+					if ((int)lane == first)
+						atomicAdd(&h[d0], (uint32_t)__popcll(m));
+				} else if (act) {
+					atomicAdd(&h[dg], 1u);
+				}
+			}
+		}
+	}
+	__syncthreads();
+	if (h[tid])
+		atomicAdd(&dev->hist[pass][tid], h[tid]);
+}
+
+// Emit: every considered row at or below the threshold goes to a result slot,
+// one counter add per wave. A slot at or past k_eff is counted, never
+// written; the host compares the count with k_eff.
+template <bool MASKED>
+__global__ void __launch_bounds__(THREADS)
+k_sel_emit(const double *__restrict__ dists, uint64_t n,
+           const uint64_t *__restrict__ mask,
+           const uint64_t *__restrict__ ids, SelDev *dev, Cand *out,
+           uint32_t k_eff) {
+	__shared__ uint32_t h[256];
+	__shared__ SelState st;
+	const SelState s = sel_enter(dev, SEL_PASSES, k_eff, h, &st);
+	const uint32_t tid = threadIdx.x, lane = tid & 63u;
+	for (uint64_t base = (uint64_t)blockIdx.x * THREADS; base < n;
+	     base += (uint64_t)gridDim.x * THREADS) {
+		const uint64_t r = base + tid;
+		bool sel = r < n;
+		if (MASKED && sel)
+			sel = (mask[r >> 6] >> (r & 63)) & 1ULL;
+		const double v = r < n ? dists[r] : 0.0;
+		sel = sel && sel_below(sel_total_key(v), (uint32_t)r, s);
+		const unsigned long long m = __ballot(sel);
+		if (m) {
+			const int first = __ffsll(m) - 1;
+			uint32_t slot0 = 0;
+			if ((int)lane == first)
+				slot0 = atomicAdd(&dev->head.count, (uint32_t)__popcll(m));
+			slot0 = (uint32_t)__shfl((int)slot0, first);
+			const uint32_t slot =
+			    slot0 + (uint32_t)__popcll(m & ((1ULL << lane) - 1));
+			if (sel && slot < k_eff)
+				out[slot] = Cand{v, ids[r]};
+		}
+	}
+}
+
+// ---------------------------------------------------------------------------
 // C-ABI implementation
 // ---------------------------------------------------------------------------
 extern "C" {
@@ -3642,6 +3903,12 @@ void sdbv_shutdown(sdbv_ctx *ctx) {
 		(void)hipHostFree(ctx->flt_mask_pin);
 	if (ctx->flt_rows_pin)
 		(void)hipHostFree(ctx->flt_rows_pin);
+	if (ctx->sel_dists)
+		(void)hipFree(ctx->sel_dists);
+	if (ctx->sel_dev)
+		(void)hipFree(ctx->sel_dev);
+	if (ctx->sel_pin)
+		(void)hipHostFree(ctx->sel_pin);
 	if (ctx->blas)
 		(void)rocblas_destroy_handle(ctx->blas);
 	(void)hipEventDestroy(ctx->ev0);
@@ -4328,8 +4595,9 @@ static void launch_all_dists(sdbv_ctx *ctx, Table &t, const float *q,
 }
 
 // All-distances launch + exact host selection: the route for k beyond the
-// scan kernel's LDS top-K window (MAX_K), and the product path proper for
-// the six non-headline metrics (SURVEY §8 a2 closure). ids are strictly
+// scan kernel's LDS top-K window (MAX_K) and for the six non-headline
+// metrics (SURVEY §8 a2 closure) whenever knn_all_dists_route does not take
+// the device select. ids are strictly
 // increasing, so (dist, row) order equals the contract's (dist, id)
 // order. Costs one n-f64 D2H per query. Under a filter (allow not null:
 // ceil(n / 64) validated words) the host selection skips the rows the bitmap
@@ -4395,6 +4663,133 @@ static int knn_large_k(sdbv_ctx *ctx, Table &t, const float *q, uint32_t d,
 		out_dists[i] = hd[e.second];
 	}
 	return SDBV_OK;
+}
+
+// Host side of the device select (kernels: "Device select of the
+// all-distances route", above the C-ABI block).
+static int ensure_cap(sdbv_ctx *ctx, void **buf, uint64_t *cap, uint64_t need);
+static int upload_filter_mask(sdbv_ctx *ctx, const Table &t,
+                              const uint64_t *allow, uint64_t allow_words);
+// All-distances launch + device select (last_scan_path 21, 22 under a
+// bitmap). count = the rows considered: t.n, or the allowed rows of the
+// filtered call (at least 1, its bitmap validated). The bitmap only reaches
+// the select; the distance kernel computes every row. Caller holds ctx->mu.
+static int knn_device_select(sdbv_ctx *ctx, Table &t, const float *q,
+                             uint32_t d, uint32_t k, const uint64_t *allow,
+                             uint64_t count, uint64_t *out_ids,
+                             double *out_dists, uint32_t *out_n) {
+	const uint32_t k_eff = (uint32_t)(k < count ? k : count);
+	int rc = ensure_query_scratch(ctx, d, 1, 1);
+	if (rc != SDBV_OK)
+		return rc;
+	rc = stage_query(ctx, q, d, d * sizeof(float));
+	if (rc != SDBV_OK)
+		return rc;
+	const uint64_t res_bytes = sizeof(SelHead) + (uint64_t)k_eff * sizeof(Cand);
+	if ((rc = ensure_cap(ctx, (void **)&ctx->sel_dists, &ctx->sel_dists_cap,
+	                     t.n * sizeof(double))) ||
+	    (rc = ensure_cap(ctx, &ctx->sel_dev, &ctx->sel_dev_cap,
+	                     sizeof(SelDev) + (uint64_t)k_eff * sizeof(Cand))))
+		return rc;
+	if (ctx->sel_pin_cap < res_bytes) {
+		if (ctx->sel_pin)
+			(void)hipHostFree(ctx->sel_pin);
+		ctx->sel_pin = nullptr;
+		ctx->sel_pin_cap = 0;
+		HIP_CHECK(ctx, hipHostMalloc(&ctx->sel_pin, res_bytes));
+		ctx->sel_pin_cap = res_bytes;
+	}
+	if (allow) {
+		rc = upload_filter_mask(ctx, t, allow, (t.n + 63) / 64);
+		if (rc != SDBV_OK)
+			return rc;
+	}
+	SelDev *dev = (SelDev *)ctx->sel_dev;
+	Cand *res_dev = (Cand *)((char *)ctx->sel_dev + sizeof(SelDev));
+	const uint64_t span = (uint64_t)THREADS * SEL_CHUNKS;
+	uint64_t nb = (t.n + span - 1) / span;
+	nb = nb < 1 ? 1 : nb > SEL_MAX_BLOCKS ? SEL_MAX_BLOCKS : nb;
+
+	HIP_CHECK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+	launch_all_dists(ctx, t, q, ctx->sel_dists);
+	HIP_CHECK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+	HIP_CHECK(ctx, hipMemsetAsync(dev, 0, sizeof(SelDev), ctx->stream));
+	for (int pass = 0; pass < SEL_PASSES; pass++) {
+		if (allow)
+			hipLaunchKernelGGL(k_sel_hist<true>, dim3((uint32_t)nb),
+			                   dim3(THREADS), 0, ctx->stream, ctx->sel_dists,
+			                   t.n, ctx->flt_mask, dev, pass, k_eff);
+		else
+			hipLaunchKernelGGL(k_sel_hist<false>, dim3((uint32_t)nb),
+			                   dim3(THREADS), 0, ctx->stream, ctx->sel_dists,
+			                   t.n, (const uint64_t *)nullptr, dev, pass, k_eff);
+	}
+	if (allow)
+		hipLaunchKernelGGL(k_sel_emit<true>, dim3((uint32_t)nb), dim3(THREADS),
+		                   0, ctx->stream, ctx->sel_dists, t.n, ctx->flt_mask,
+		                   t.ids_dev, dev, res_dev, k_eff);
+	else
+		hipLaunchKernelGGL(k_sel_emit<false>, dim3((uint32_t)nb), dim3(THREADS),
+		                   0, ctx->stream, ctx->sel_dists, t.n,
+		                   (const uint64_t *)nullptr, t.ids_dev, dev, res_dev,
+		                   k_eff);
+	HIP_CHECK(ctx, hipEventRecord(ctx->ev2, ctx->stream));
+	HIP_CHECK(ctx, hipMemcpyAsync(ctx->sel_pin, &dev->head, res_bytes,
+	                              hipMemcpyDeviceToHost, ctx->stream));
+	HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+	HIP_CHECK(ctx, hipGetLastError());
+
+	float ms_dist = 0, ms_sel = 0;
+	(void)hipEventElapsedTime(&ms_dist, ctx->ev0, ctx->ev1);
+	(void)hipEventElapsedTime(&ms_sel, ctx->ev1, ctx->ev2);
+	ctx->stats.last_scan_kernel_ms = ms_dist;
+	ctx->stats.last_merge_kernel_ms = ms_sel;
+	ctx->stats.last_scan_path = allow ? 22u : 21u;
+	if (!allow)
+		ctx->stats.last_rows_scanned = t.n;
+
+	const SelHead *head = (const SelHead *)ctx->sel_pin;
+	if (head->count != k_eff) {
+		ctx->err = "device select: emitted " + std::to_string(head->count) +
+		           " rows, expected " + std::to_string(k_eff);
+		return SDBV_ERR_HIP;
+	}
+	Cand *res = (Cand *)((char *)ctx->sel_pin + sizeof(SelHead));
+	std::sort(res, res + k_eff, [](const Cand &a, const Cand &b) {
+		const uint64_t ka = sel_total_key(a.dist), kb = sel_total_key(b.dist);
+		return ka != kb ? ka < kb : a.id < b.id;
+	});
+	copy_results(res, k_eff, out_ids, out_dists, out_n);
+	return SDBV_OK;
+}
+
+// SDBV_SELECT_DEVICE / SDBV_SELECT_DEVICE_MIN_ROWS, read at each call.
+static bool select_device_policy(const Table &t) {
+	return shadow_policy(&t, "SDBV_SELECT_DEVICE", "SDBV_SELECT_DEVICE_MIN_ROWS",
+	                     SEL_DEFAULT_MIN_ROWS);
+}
+
+// The all-distances route of sdbv_knn_bruteforce, _filtered and the non-GEMM
+// sdbv_knn_batch: the device select when k <= SEL_MAX_K, the rows fit 32-bit
+// indices and the policy admits the table; otherwise knn_large_k, unchanged.
+// count as for knn_device_select. last_total_ms is the wall time of either.
+static int knn_all_dists_route(sdbv_ctx *ctx, Table &t, const float *q,
+                               uint32_t d, uint32_t k, const uint64_t *allow,
+                               uint64_t count, uint64_t *out_ids,
+                               double *out_dists, uint32_t *out_n) {
+	auto t_start = std::chrono::steady_clock::now();
+	int rc;
+	if (k <= SEL_MAX_K && count > 0 && t.n < (1ULL << 32) &&
+	    select_device_policy(t))
+		rc = knn_device_select(ctx, t, q, d, k, allow, count, out_ids,
+		                       out_dists, out_n);
+	else
+		rc = knn_large_k(ctx, t, q, d, k, allow, out_ids, out_dists, out_n);
+	ctx->stats.last_total_ms =
+	    std::chrono::duration<double, std::milli>(
+	        std::chrono::steady_clock::now() - t_start)
+	        .count();
+	return rc;
 }
 
 // Row-span grid of the prefilter sweep of shadow tier kind (1..3 and 5; 4 =
@@ -4788,8 +5183,8 @@ int sdbv_knn_bruteforce(sdbv_ctx *ctx, uint64_t table, const float *q,
 	ctx->stats.last_prefilter_candidates = 0;
 	ctx->stats.last_prefilter_stage1 = 0;
 	if (k > MAX_K || t.metric > SDBV_METRIC_EUCLIDEAN)
-		return knn_large_k(ctx, t, q, d, k, nullptr, out_ids, out_dists,
-		                   out_n);
+		return knn_all_dists_route(ctx, t, q, d, k, nullptr, t.n, out_ids,
+		                           out_dists, out_n);
 
 	uint64_t rows_per_block = 0;
 	const uint64_t nblocks = scan_grid(t.n, &rows_per_block);
@@ -4905,6 +5300,56 @@ uint64_t sdbv_filter_rows(const uint64_t *allow, uint64_t allow_words,
 		count += pc;
 	}
 	return count;
+}
+
+// Host-only twin of the device select: the same digit walk (sel_match,
+// sel_digit, sel_step) on host histograms, then the rows at or below the
+// threshold in result order.
+int sdbv_select_topk(const double *dists, uint64_t n, const uint64_t *allow,
+                     uint32_t k, uint32_t *out_rows, uint32_t *out_n) {
+	if (!out_n || (n && !dists) || n >= (1ULL << 32))
+		return SDBV_ERR_BAD_ARG;
+	auto allowed = [&](uint64_t r) {
+		return !allow || ((allow[r >> 6] >> (r & 63)) & 1ULL);
+	};
+	uint64_t count = 0;
+	for (uint64_t r = 0; r < n; r++)
+		count += allowed(r) ? 1 : 0;
+	const uint32_t k_eff = (uint32_t)(k < count ? k : count);
+	*out_n = 0;
+	if (k_eff == 0)
+		return SDBV_OK;
+	if (!out_rows)
+		return SDBV_ERR_BAD_ARG;
+	SelState s{0, 0, k_eff, 0, 0};
+	uint32_t hist[256];
+	for (int pass = 0; pass < SEL_PASSES && !s.done; pass++) {
+		std::memset(hist, 0, sizeof(hist));
+		for (uint64_t r = 0; r < n; r++) {
+			if (!allowed(r))
+				continue;
+			const uint64_t key = sel_total_key(dists[r]);
+			if (sel_match(key, (uint32_t)r, s, pass))
+				hist[sel_digit(key, (uint32_t)r, pass)]++;
+		}
+		sel_step(hist, pass, &s);
+	}
+	std::vector<std::pair<uint64_t, uint32_t>> got;
+	got.reserve(k_eff);
+	for (uint64_t r = 0; r < n; r++) {
+		if (!allowed(r))
+			continue;
+		const uint64_t key = sel_total_key(dists[r]);
+		if (sel_below(key, (uint32_t)r, s))
+			got.emplace_back(key, (uint32_t)r);
+	}
+	if (!s.done || got.size() != k_eff)
+		return SDBV_ERR_HIP; // the walk disagrees with itself: never expected
+	std::sort(got.begin(), got.end());
+	for (uint32_t i = 0; i < k_eff; i++)
+		out_rows[i] = got[i].second;
+	*out_n = k_eff;
+	return SDBV_OK;
 }
 
 // SDBV_FILTER_ROWLIST_MAX, read at each call: the largest allowed-row count
@@ -5053,7 +5498,8 @@ int sdbv_knn_bruteforce_filtered(sdbv_ctx *ctx, uint64_t table, const float *q,
 		return SDBV_OK;
 	}
 	if (!device_topk)
-		return knn_large_k(ctx, t, q, d, k, allow, out_ids, out_dists, out_n);
+		return knn_all_dists_route(ctx, t, q, d, k, allow, count, out_ids,
+		                           out_dists, out_n);
 
 	const bool by_list = count <= list_max;
 	double q_norm = sqrt((double)h_sumsq_f32(q, d));
@@ -5222,9 +5668,10 @@ int sdbv_knn_batch(sdbv_ctx *ctx, uint64_t table, const float *Q, uint32_t b,
 		// batch path is only for the genuinely dense cosine/euclidean case)
 		for (uint32_t j = 0; j < b; j++) {
 			uint32_t m = 0;
-			int rc = knn_large_k(ctx, t, Q + (uint64_t)j * d, d, k, nullptr,
-			                     out_ids + (uint64_t)j * k,
-			                     out_dists + (uint64_t)j * k, &m);
+			int rc = knn_all_dists_route(ctx, t, Q + (uint64_t)j * d, d, k,
+			                             nullptr, t.n,
+			                             out_ids + (uint64_t)j * k,
+			                             out_dists + (uint64_t)j * k, &m);
 			if (rc)
 				return rc;
 			for (uint32_t i = m; i < k; i++) {
