@@ -585,22 +585,261 @@ __global__ __launch_bounds__(THREADS) void k_scan(
 	scan_topk_write(topk, topk_n, k, ids, block_out);
 }
 
-// Final merge: one block selects global top-k from nblocks*k candidates.
-// block_out is mutable scratch: selected entries are poisoned to +inf
-// (same-workgroup global visibility ordered by __syncthreads()).
-// Exact k-selection over a candidate slab. Each BLOCK merges its slice
-// [per_block*g, per_block*(g+1)) into out[g*k..]: grid 1 with per_block =
-// total is the classic single-block merge; a two-level tree (G slices,
-// then one block over G*k) cuts the 1954-block scan's merge latency
-// (top-k of per-slice top-ks == the global top-k, exactly).
+// Exact k-selection over a candidate slab, in one pass over its entries.
+// Each BLOCK merges its slice [per_block*g, per_block*(g+1)) into
+// out[g*k..]: grid 1 with per_block = total is the classic single-block
+// merge; a two-level tree (G slices, then one block over G*k) cuts the
+// 1954-block scan's merge latency (top-k of per-slice top-ks == the global
+// top-k, exactly). The input is read once and never written.
+//
+// block_select_slice<NT, E> is the body, for a block of NT threads. A thread
+// holds E strided entries of a chunk of NT * E in registers, as
+// (total_key(dist), id), plus one survivor of the chunks before it. The
+// block walks the 128-bit (key, id) from its top byte with a 256-bin LDS
+// histogram over the entries under the prefix found so far, until the bin it
+// steps into holds exactly the entries still needed (at most 16 passes of
+// three barriers; the bytes all keys share are skipped). Entries below the
+// prefix and as many under it as are still needed go to LDS: at most k, and
+// entries that tie through all 16 bytes are the same value. The survivors of
+// the last chunk are ordered by rank counting and written with their dist
+// restored from the key (the key is a bijection of the bits). An entry
+// {all-ones NaN, ~0} never compared below the old round loop's start value
+// and is left out here as it was there. The round loop poisoned a winner
+// with the pad value {+inf, ~0}, which then won every later round against
+// an entry above it (a positive NaN): such an entry came out in slot 0 or
+// not at all, the pad in its place, and so it does here. No barrier or memory round trip
+// depends on k. out may be LDS or global; a closing barrier makes it
+// visible to the block.
+struct SliceSel {
+	uint32_t hist[256];
+	uint32_t wsum[4];
+	unsigned long long k_and, k_or;
+	uint64_t pk, pid; // the prefix: bytes of passes < pass, zero below
+	uint32_t need;    // entries still to take from under the prefix
+	uint32_t state;   // 0 walking, 1 prefix final after pend, 2 take all
+	uint32_t pend;
+	uint32_t nsel, neq;
+	uint64_t skey[MAX_K], sid[MAX_K];
+};
+
+// Whether (key, id) lies under the prefix of passes 0..p-1.
+__device__ __forceinline__ static bool slice_under(uint64_t key, uint64_t id,
+                                                   uint64_t pk, uint64_t pid,
+                                                   uint32_t p) {
+	if (p == 0)
+		return true;
+	if (p < 8)
+		return (key >> (64 - 8 * p)) == (pk >> (64 - 8 * p));
+	if (key != pk)
+		return false;
+	if (p == 8)
+		return true;
+	return (id >> (128 - 8 * p)) == (pid >> (128 - 8 * p));
+}
+
+// Whether (key, id) lies below the prefix of passes 0..p-1 (p >= 1).
+__device__ __forceinline__ static bool slice_below(uint64_t key, uint64_t id,
+                                                   uint64_t pk, uint64_t pid,
+                                                   uint32_t p) {
+	if (p <= 8)
+		return p == 8 ? key < pk : (key >> (64 - 8 * p)) < (pk >> (64 - 8 * p));
+	if (key != pk)
+		return key < pk;
+	return p == 16 ? id < pid
+	               : (id >> (128 - 8 * p)) < (pid >> (128 - 8 * p));
+}
+
+template <int NT, int E>
+__device__ __forceinline__ static void block_select_slice(
+    const Cand *__restrict__ in, uint64_t len, uint32_t k, Cand *out,
+    SliceSel *S) {
+	static_assert(NT >= MAX_K && NT <= 256 && 256 % NT == 0 && E < 32, "");
+	constexpr int BPT = 256 / NT; // histogram bins a thread owns
+	const uint32_t tid = threadIdx.x;
+	const uint32_t lane = tid & 63, wave = tid >> 6;
+	uint64_t ek[E + 1], eid[E + 1];
+	uint32_t vm = 0; // valid entries; bit E is the carried survivor
+
+	for (uint64_t c0 = 0; c0 == 0 || c0 < len; c0 += (uint64_t)NT * E) {
+		vm &= 1u << E;
+#pragma unroll
+		for (int e = 0; e < E; e++) {
+			const uint64_t i = c0 + (uint64_t)e * NT + tid;
+			ek[e] = ~0ULL;
+			eid[e] = ~0ULL;
+			if (i < len) {
+				const Cand c = in[i];
+				ek[e] = d_total_key(c.dist);
+				eid[e] = c.id;
+				if (ek[e] != ~0ULL || eid[e] != ~0ULL)
+					vm |= 1u << e;
+			}
+		}
+		// the bytes every key shares need no pass
+		uint64_t ka = ~0ULL, ko = 0;
+#pragma unroll
+		for (int e = 0; e <= E; e++)
+			if ((vm >> e) & 1u) {
+				ka &= ek[e];
+				ko |= ek[e];
+			}
+		for (int off = 32; off > 0; off >>= 1) {
+			ka &= __shfl_xor(ka, off);
+			ko |= __shfl_xor(ko, off);
+		}
+		if (tid == 0) {
+			S->k_and = ~0ULL;
+			S->k_or = 0;
+			S->nsel = 0;
+			S->neq = 0;
+			S->state = 0;
+		}
+#pragma unroll
+		for (int b = 0; b < BPT; b++)
+			S->hist[tid * BPT + b] = 0;
+		__syncthreads();
+		if (lane == 0) {
+			atomicAnd(&S->k_and, (unsigned long long)ka);
+			atomicOr(&S->k_or, (unsigned long long)ko);
+		}
+		__syncthreads();
+		const uint64_t kx = S->k_and ^ S->k_or;
+		// all keys equal (or no entry at all): the walk starts on the ids
+		uint32_t p = S->k_and > S->k_or ? 0u
+		             : kx == 0         ? 8u
+		                               : (uint32_t)__clzll((long long)kx) / 8u;
+		uint64_t pk = p == 0 ? 0 : S->k_and & (~0ULL << (64 - 8 * p));
+		uint64_t pid = 0;
+		uint32_t need = k;
+		uint32_t state = 0;
+
+		for (; p < 16; p++) {
+			const uint32_t sh = p < 8 ? 56 - 8 * p : 120 - 8 * p;
+#pragma unroll
+			for (int e = 0; e <= E; e++)
+				if (((vm >> e) & 1u) &&
+				    slice_under(ek[e], eid[e], pk, pid, p))
+					atomicAdd(&S->hist[((p < 8 ? ek[e] : eid[e]) >> sh) & 255u],
+					          1u);
+			__syncthreads();
+			uint32_t c[BPT], mine = 0;
+#pragma unroll
+			for (int b = 0; b < BPT; b++) {
+				c[b] = S->hist[tid * BPT + b];
+				S->hist[tid * BPT + b] = 0; // own bins: ready for the next pass
+				mine += c[b];
+			}
+			uint32_t incl = mine;
+			for (int off = 1; off < 64; off <<= 1) {
+				const uint32_t o = __shfl_up(incl, off);
+				if (lane >= (uint32_t)off)
+					incl += o;
+			}
+			if (lane == 63)
+				S->wsum[wave] = incl;
+			__syncthreads();
+			uint32_t acc = incl - mine, total = 0;
+#pragma unroll
+			for (int w = 0; w < NT / 64; w++) {
+				const uint32_t ws = S->wsum[w];
+				acc += (uint32_t)w < wave ? ws : 0u;
+				total += ws;
+			}
+			if (total < need) { // only before the first step: fewer than k
+				if (tid == 0)
+					S->state = 2;
+			} else {
+#pragma unroll
+				for (int b = 0; b < BPT; b++) {
+					if (c[b] != 0 && acc < need && acc + c[b] >= need) {
+						const uint64_t dg = (uint64_t)(tid * BPT + b) << sh;
+						S->pk = p < 8 ? pk | dg : pk;
+						S->pid = p < 8 ? 0 : pid | dg;
+						S->need = need - acc;
+						S->pend = p + 1;
+						S->state = (c[b] == need - acc || p == 15) ? 1u : 0u;
+					}
+					acc += c[b];
+				}
+			}
+			__syncthreads();
+			state = S->state;
+			if (state == 2)
+				break;
+			pk = S->pk;
+			pid = S->pid;
+			need = S->need;
+			if (state == 1)
+				break;
+		}
+		// state 0 here: every entry ties on the key and the walk never ran
+		// (p started at 16 cannot happen; p == 8 start always steps), so
+		// state is 1 or 2
+		const uint32_t pend = state == 1 ? S->pend : 0;
+#pragma unroll
+		for (int e = 0; e <= E; e++) {
+			if (!((vm >> e) & 1u))
+				continue;
+			bool take = state == 2;
+			if (!take) {
+				take = slice_below(ek[e], eid[e], pk, pid, pend);
+				if (!take && slice_under(ek[e], eid[e], pk, pid, pend))
+					take = atomicAdd(&S->neq, 1u) < need;
+			}
+			if (take) {
+				const uint32_t pos = atomicAdd(&S->nsel, 1u);
+				if (pos < MAX_K) { // always: at most k are taken
+					S->skey[pos] = ek[e];
+					S->sid[pos] = eid[e];
+				}
+			}
+		}
+		__syncthreads();
+		const uint32_t m = S->nsel;
+		if (c0 + (uint64_t)NT * E < len) { // carry the survivors
+			vm = 0;
+			if (tid < m) {
+				ek[E] = S->skey[tid];
+				eid[E] = S->sid[tid];
+				vm = 1u << E;
+			}
+			__syncthreads();
+			continue;
+		}
+		// last chunk: order by rank counting, ties broken by LDS position
+		if (tid < m) {
+			const uint64_t kt = S->skey[tid], it = S->sid[tid];
+			uint32_t rank = 0;
+			for (uint32_t j = 0; j < m; j++) {
+				const uint64_t kj = S->skey[j], ij = S->sid[j];
+				rank += (kj < kt ||
+				         (kj == kt && (ij < it || (ij == it && j < tid))))
+				            ? 1u
+				            : 0u;
+			}
+			Cand o;
+			o.dist = __longlong_as_double(
+			    (long long)((kt >> 63) ? (kt & 0x7FFFFFFFFFFFFFFFULL) : ~kt));
+			o.id = it;
+			if (rank > 0 && kt > 0xFFF0000000000000ULL) { // above the pad
+				o.dist = __longlong_as_double(0x7FF0000000000000LL);
+				o.id = ~0ULL;
+			}
+			out[rank] = o;
+		} else if (tid < k) { // slice shorter than k: pad
+			Cand o;
+			o.dist = __longlong_as_double(0x7FF0000000000000LL);
+			o.id = ~0ULL;
+			out[tid] = o;
+		}
+		__syncthreads();
+	}
+}
+
 __device__ __forceinline__ static void merge_slice(
-    Cand *__restrict__ block_out, uint64_t total, uint32_t k,
+    const Cand *__restrict__ block_out, uint64_t total, uint32_t k,
     uint64_t per_block, Cand *__restrict__ out) {
-	__shared__ uint64_t red_key[THREADS / 64];
-	__shared__ uint64_t red_id[THREADS / 64];
-	__shared__ long red_idx[THREADS / 64];
-	const int lane = threadIdx.x & 63;
-	const int wave = threadIdx.x >> 6;
+	__shared__ SliceSel sel;
 	const uint64_t s0 = (uint64_t)blockIdx.x * per_block;
 	const uint64_t s1 = s0 + per_block < total ? s0 + per_block : total;
 	out += (uint64_t)blockIdx.x * k;
@@ -611,65 +850,11 @@ __device__ __forceinline__ static void merge_slice(
 		}
 		return;
 	}
-	for (int slot = 0; slot < (int)k; slot++) {
-		uint64_t bk = ~0ULL;
-		uint64_t bid = ~0ULL;
-		long bi = -1;
-		for (uint64_t i = s0 + threadIdx.x; i < s1; i += THREADS) {
-			uint64_t ck = d_total_key(block_out[i].dist);
-			uint64_t cid = block_out[i].id;
-			if (ck < bk || (ck == bk && cid < bid)) {
-				bk = ck;
-				bid = cid;
-				bi = (long)i;
-			}
-		}
-		for (int off = 32; off > 0; off >>= 1) {
-			uint64_t ok = __shfl_down(bk, off);
-			uint64_t oid = __shfl_down(bid, off);
-			long oi = __shfl_down(bi, off);
-			if (ok < bk || (ok == bk && oid < bid)) {
-				bk = ok;
-				bid = oid;
-				bi = oi;
-			}
-		}
-		if (lane == 0) {
-			red_key[wave] = bk;
-			red_id[wave] = bid;
-			red_idx[wave] = bi;
-		}
-		__syncthreads();
-		if (threadIdx.x == 0) {
-			uint64_t bbk = ~0ULL, bbid = ~0ULL;
-			long best = -1;
-			for (int w = 0; w < THREADS / 64; w++) {
-				if (red_idx[w] < 0)
-					continue;
-				if (red_key[w] < bbk ||
-				    (red_key[w] == bbk && red_id[w] < bbid)) {
-					bbk = red_key[w];
-					bbid = red_id[w];
-					best = red_idx[w];
-				}
-			}
-			if (best < 0) { // slice shorter than k: pad
-				out[slot].dist =
-				    __longlong_as_double(0x7FF0000000000000LL);
-				out[slot].id = ~0ULL;
-			} else {
-				out[slot] = block_out[best];
-				block_out[best].dist =
-				    __longlong_as_double(0x7FF0000000000000LL);
-				block_out[best].id = ~0ULL;
-			}
-		}
-		__syncthreads();
-	}
+	block_select_slice<THREADS, 16>(block_out + s0, s1 - s0, k, out, &sel);
 }
 
 __global__ __launch_bounds__(THREADS) void k_merge(
-    Cand *__restrict__ block_out, uint64_t total, uint32_t k,
+    const Cand *__restrict__ block_out, uint64_t total, uint32_t k,
     uint64_t per_block, Cand *__restrict__ out) {
 	merge_slice(block_out, total, k, per_block, out);
 }
@@ -2112,16 +2297,29 @@ __global__ __launch_bounds__(THREADS) void k_pf_final(
 // Exact distances of the K rows with the smallest H-only upper bounds
 // (approx_top of launch_merge_tree: id = row position), one 64-lane
 // workgroup each: out[c] = rows_exact<0> of row approx_top[c].id, or +inf
-// for an entry without a row (fewer than K rows carry a bound).
+// for an entry without a row (fewer than K rows carry a bound). With
+// fold_total > 0, approx_top is the merge tree's level 1 instead
+// (fold_total <= 32 * MAX_K winners): every workgroup selects the K smallest
+// of them itself, which is the tree's level 2 without its launch, and takes
+// its own entry.
 __global__ __launch_bounds__(64) void k_pf4_threshold(
     const float *__restrict__ cm, const double *__restrict__ norms,
     const uint64_t *__restrict__ ids, uint64_t n_pad, uint32_t d,
     const float *__restrict__ qg, double q_norm,
-    const Cand *__restrict__ approx_top, Cand *__restrict__ out) {
+    const Cand *__restrict__ approx_top, uint32_t fold_total, uint32_t k,
+    Cand *__restrict__ out) {
 	__shared__ float qs[MAX_D];
 	__shared__ float xs[MAX_D];
 	__shared__ float ps[8];
-	const uint64_t r = approx_top[blockIdx.x].id;
+	__shared__ SliceSel sel;
+	__shared__ Cand top[MAX_K];
+	uint64_t r;
+	if (fold_total > 0) { // uniform
+		block_select_slice<64, 16>(approx_top, fold_total, k, top, &sel);
+		r = top[blockIdx.x].id;
+	} else {
+		r = approx_top[blockIdx.x].id;
+	}
 	if (r == ~0ULL) { // uniform
 		if (threadIdx.x == 0) {
 			Cand o;
@@ -4543,16 +4741,26 @@ static void launch_scan(sdbv_ctx *ctx, Table &t, uint32_t k, double q_norm,
 
 // The k_merge tree over the nblocks * k block winners in ctx->block_out:
 // the top-k lands in ctx->final_out. Top-k of per-slice top-ks is the global
-// top-k, exactly.
-static void launch_merge_tree(sdbv_ctx *ctx, uint64_t nblocks, uint32_t k) {
+// top-k, exactly. A caller whose next kernel folds level 2 into itself
+// passes fold: of a two-level tree only level 1 then runs, *fold receives
+// the G * k winners it left in ctx->merge_tmp, and ctx->final_out is not
+// written; a single-level tree runs whole and leaves *fold 0.
+static void launch_merge_tree(sdbv_ctx *ctx, uint64_t nblocks, uint32_t k,
+                              uint32_t *fold = nullptr) {
 	uint64_t total = nblocks * k;
 	const uint64_t G = 32; // level-1 fan-in
+	if (fold)
+		*fold = 0;
 	if (total > 4096 && nblocks > G) {
 		// two levels: G slices in parallel, then one block over G * k
 		uint64_t per = ((nblocks + G - 1) / G) * k;
 		hipLaunchKernelGGL(k_merge, dim3((uint32_t)G), dim3(THREADS), 0,
 		                   ctx->stream, (Cand *)ctx->block_out, total, k, per,
 		                   (Cand *)ctx->merge_tmp);
+		if (fold) {
+			*fold = (uint32_t)(G * k);
+			return;
+		}
 		hipLaunchKernelGGL(k_merge, dim3(1), dim3(THREADS), 0, ctx->stream,
 		                   (Cand *)ctx->merge_tmp, G * k, k, G * k,
 		                   (Cand *)ctx->final_out);
@@ -5089,14 +5297,17 @@ static int knn_prefilter_h4(sdbv_ctx *ctx, Table &t, uint32_t k, double q_norm,
 	                   rows_per_block, ctx->pf_scores, (Cand *)ctx->block_out,
 	                   cand_cnt, (const uint64_t *)nullptr);
 	HIP_CHECK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
-	// K smallest H-only upper bounds -> final_out, id = row position
-	launch_merge_tree(ctx, nblocks, k);
+	// K smallest H-only upper bounds, id = row position: in final_out, or
+	// as level-1 winners in merge_tmp that k_pf4_threshold selects from
+	uint32_t fold = 0;
+	launch_merge_tree(ctx, nblocks, k, &fold);
 	HIP_CHECK(ctx, hipEventRecord(ctx->ev2, ctx->stream));
 	{
 		hipLaunchKernelGGL(k_pf4_threshold, dim3(k), dim3(64), 0, ctx->stream,
 		                   t.cm, t.norms, t.ids_dev, t.n_pad, t.d, ctx->q_dev,
-		                   q_norm, (const Cand *)ctx->final_out,
-		                   (Cand *)ctx->pf4_thr);
+		                   q_norm,
+		                   (const Cand *)(fold ? ctx->merge_tmp : ctx->final_out),
+		                   fold, k, (Cand *)ctx->pf4_thr);
 		uint64_t ngrp = (t.n + 3) / 4;
 		uint64_t nb = (ngrp + THREADS * PF4_PASSES - 1) / (THREADS * PF4_PASSES);
 		if (nb > 512)
