@@ -138,6 +138,14 @@ typedef struct sdbv_stats {
 	                               overflowed in the last sdbv_knn_batch call
 	                               and all rows were selected again through
 	                               the rocBLAS pass, else 0 */
+	double last_append_ms;        /* host wall of the last sdbv_append_rows call
+	                                 that added rows, its synchronisation
+	                                 included */
+	double last_append_kernel_ms; /* HIP-event time of that call's append
+	                                 kernel and shadow update (a regrowth is
+	                                 not in it) */
+	uint32_t last_append_realloc; /* 0 if that call wrote in place, 1 if it
+	                                 regrew the table's store first */
 } sdbv_stats;
 
 /* Create a context on HIP device `device` (-1 = current device). */
@@ -154,7 +162,8 @@ int sdbv_get_stats(sdbv_ctx *, sdbv_stats *out);
  * must be strictly increasing (NULL => 0..n-1); result tie-break is
  * (distance asc, id asc), which equals the reference's orderings for
  * monotone ids (knn.rs:363 BTreeSet<(FloatKey, VectorId)>, knn_topk.rs:61-73
- * insertion-order seq). Restages (replaces) if `table` already staged.
+ * insertion-order seq). Restages (replaces) if `table` already staged;
+ * sdbv_append_rows adds rows behind the staged ones without restaging.
  *
  * Memory: d*4 + 20 B per row. A COSINE table of at least
  * SDBV_SCAN_PREFILTER_MIN_ROWS rows (environment, default 500000) also gets
@@ -297,6 +306,55 @@ int sdbv_prefilter_q12(const float *q, uint32_t d, int16_t *codes, float *sq,
 
 uint64_t sdbv_table_rows(sdbv_ctx *, uint64_t table);
 int sdbv_drop_table(sdbv_ctx *, uint64_t table);
+
+/* Append m row-major rows to a table staged by sdbv_stage_corpus or
+ * sdbv_stage_synthetic, without restaging it. `ids` must be strictly
+ * increasing with ids[0] above the table's last staged id (NULL => last id
+ * + 1, + 2, ...), which keeps the tie-break contract of sdbv_stage_corpus. A
+ * row whose id sorts INSIDE the staged range, and a change to a staged row,
+ * still need a restage. After SDBV_OK every search entry point answers in
+ * every bit (ids, distance bits, *out_n, and the path and candidate counts
+ * of sdbv_stats) as if the table had been staged once with the concatenated
+ * rows and ids. Synchronous; holds the context mutex.
+ *
+ * Capacity: a table's column stride n_pad is also its capacity
+ * (sdbv_table_capacity). Rows that fit (n + m <= n_pad) are written in place
+ * by one kernel: transpose into the feature-major store, norms, batch aux and
+ * ids of the new rows only, then the table's prefilter shadow over the
+ * 256-row blocks that hold them; the call allocates nothing once the
+ * context's staging buffer exists (rows pass through it in chunks of at most
+ * 256 MiB). Rows that do not fit regrow the store first, to
+ * sdbv_append_capacity(n_pad, n + m): new arrays are allocated BEFORE the
+ * old ones are freed (peak device memory: old plus new store), the store is
+ * copied, and the shadow is rebuilt at the new capacity with its kind and
+ * side data (one pass over the store; a shadow that no longer fits is
+ * dropped and the append still succeeds). Growth is geometric, so a stream
+ * of appends pays O(log n) regrowths; sdbv_table_reserve avoids them. A table
+ * keeps the shadow it has: the staging policy's row thresholds are not asked
+ * again. sdbv_stats.bytes_staged follows the capacity.
+ *
+ * Checked before anything is touched (a refused call leaves the table as it
+ * was): SDBV_ERR_NO_TABLE; SDBV_ERR_UNSUPPORTED for a table staged for graph
+ * search (sdbv_hnsw_finalize, sdbv_index_*); SDBV_ERR_BAD_ARG when d differs
+ * from the table's, rows == NULL with m > 0, or n + m >= 2^32;
+ * SDBV_ERR_IDS_UNSORTED when ids are not increasing or ids[0] is not above
+ * the last staged id. m == 0 is SDBV_OK and nothing happens. A failed
+ * regrowth is SDBV_ERR_OOM with the table intact. */
+int sdbv_append_rows(sdbv_ctx *, uint64_t table, const float *rows,
+                     const uint64_t *ids, uint64_t m, uint32_t d);
+/* Grow the table's capacity to at least `rows` now (rounded up to a multiple
+ * of 4096, no growth factor), as a regrowing append does; a no-op when the
+ * capacity is already that large. A bulk loader reserves once and then
+ * appends in place. Errors as for sdbv_append_rows; rows >= 2^32 is
+ * SDBV_ERR_BAD_ARG. */
+int sdbv_table_reserve(sdbv_ctx *, uint64_t table, uint64_t rows);
+/* Rows the table's store holds without regrowing; 0 = not staged. */
+uint64_t sdbv_table_capacity(sdbv_ctx *, uint64_t table);
+/* Host-only: the capacity a table of capacity n_pad has after an append that
+ * needs `need` rows: n_pad when need <= n_pad, otherwise
+ * max(need, n_pad + n_pad / 2) rounded up to a multiple of 4096 (the least
+ * common multiple of the scan tile and the shadow tiers' tiles). */
+uint64_t sdbv_append_capacity(uint64_t n_pad, uint64_t need);
 
 /* Minkowski order for a staged table (Distance::Minkowski(Number),
  * index.rs:258): call after staging; ignored by other metrics. */

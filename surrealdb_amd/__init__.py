@@ -66,6 +66,9 @@ class _Stats(ctypes.Structure):
         ("last_prefilter_stage1", ctypes.c_uint64),
         ("last_batch_exact_queries", ctypes.c_uint64),
         ("last_batch_refold", ctypes.c_uint32),
+        ("last_append_ms", ctypes.c_double),
+        ("last_append_kernel_ms", ctypes.c_double),
+        ("last_append_realloc", ctypes.c_uint32),
     ]
 
 
@@ -99,6 +102,12 @@ def lib():
     L.sdbv_table_rows.restype = u64
     L.sdbv_table_rows.argtypes = [vp, u64]
     L.sdbv_drop_table.argtypes = [vp, u64]
+    L.sdbv_append_rows.argtypes = [vp, u64, f32p, u64p, u64, u32]
+    L.sdbv_table_reserve.argtypes = [vp, u64, u64]
+    L.sdbv_table_capacity.restype = u64
+    L.sdbv_table_capacity.argtypes = [vp, u64]
+    L.sdbv_append_capacity.restype = u64
+    L.sdbv_append_capacity.argtypes = [u64, u64]
     L.sdbv_table_set_prefilter.argtypes = [vp, u64, ctypes.c_int]
     L.sdbv_table_set_prefilter_kind.argtypes = [vp, u64, ctypes.c_int]
     L.sdbv_table_set_prefilter_i6.argtypes = [vp, u64]
@@ -283,6 +292,42 @@ class Context:
 
     def drop_table(self, table):
         _check(self._ptr, lib().sdbv_drop_table(self._ptr, table), "drop_table")
+
+    def append_rows(self, table, rows, ids=None):
+        """Append the rows of an (m, d) array to a staged scan table without
+        restaging it. ids: strictly increasing and above the table's last
+        id (None = last id + 1, + 2, ...). Afterwards every search answers
+        in every bit as if the table had been staged once with all rows.
+        Rows that fit the table's capacity are written in place; otherwise
+        the store is regrown first to append_capacity(capacity, n + m)
+        (stats last_append_realloc says which, last_append_ms /
+        last_append_kernel_ms what it cost)."""
+        import numpy as np
+        rows = np.ascontiguousarray(rows, dtype=np.float32)
+        if rows.ndim != 2:
+            raise SdbvError(f"append_rows: (m, d) array expected, got "
+                            f"shape {rows.shape}")
+        m, d = rows.shape
+        idp = None
+        if ids is not None:
+            ids = np.ascontiguousarray(ids, dtype=np.uint64)
+            if ids.shape != (m,):
+                raise SdbvError(f"append_rows: {ids.size} ids for {m} rows")
+            idp = ids.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))
+        _check(self._ptr, lib().sdbv_append_rows(
+            self._ptr, table,
+            rows.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), idp, m, d),
+            "sdbv_append_rows")
+
+    def table_reserve(self, table, rows):
+        """Grow the table's capacity to at least `rows` (rounded up to a
+        multiple of 4096) so that appends up to there run in place."""
+        _check(self._ptr, lib().sdbv_table_reserve(self._ptr, table, rows),
+               "sdbv_table_reserve")
+
+    def table_capacity(self, table):
+        """Rows the table holds without regrowing; 0 = not staged."""
+        return lib().sdbv_table_capacity(self._ptr, table)
 
     def table_set_prefilter(self, table, on):
         """Build (on) or free (off) the table's bf16 prefilter shadow,
@@ -477,6 +522,13 @@ def select_topk(dists, k, allow=None):
     if rc != 0:
         raise SdbvError(f"sdbv_select_topk failed ({rc})")
     return rows[:out_n.value]
+
+
+def append_capacity(n_pad, need):
+    """Host-only: the capacity of a table of capacity n_pad after an append
+    that needs `need` rows: n_pad when it fits, else max(need, 1.5 n_pad)
+    rounded up to a multiple of 4096."""
+    return int(lib().sdbv_append_capacity(int(n_pad), int(need)))
 
 
 def prefilter_eps(d):

@@ -123,7 +123,12 @@ struct Shadow {
 
 struct Table {
 	uint64_t n = 0;
-	uint64_t n_pad = 0;
+	uint64_t n_pad = 0;       // column stride of cm and the table's capacity:
+	                          // roundup(n, TILE) as staged, a multiple of 4096
+	                          // once grown; cells [n, n_pad) are zero
+	uint64_t last_id = 0;     // id of row n - 1 (n > 0): appended ids are larger
+	bool scan_table = true;   // staged for scanning (sdbv_append_rows refuses
+	                          // a table staged for graph search)
 	uint32_t d = 0;
 	uint8_t metric = 0;
 	double order = 0.0;       // minkowski order (sdbv_table_set_order)
@@ -205,6 +210,9 @@ struct sdbv_ctx {
 	uint64_t sel_dev_cap = 0;    // bytes
 	void *sel_pin = nullptr;     // pinned: SelHead, then [k_eff] Cand
 	uint64_t sel_pin_cap = 0;    // bytes
+	// sdbv_append_rows: one chunk of new rows, row-major, then their ids
+	void *app_buf = nullptr;
+	uint64_t app_buf_cap = 0; // bytes
 };
 
 struct Cand {
@@ -922,14 +930,16 @@ __device__ static inline float d_unkey32(uint32_t k) {
 // float4 loads, one 16-byte store). pinv[r] = f32 1/norm, or NaN when the
 // bound cannot cover row r: a non-finite element, a bf16 rounding that
 // overflows, a norm outside [PF_NORM_MIN, PF_NORM_MAX] (zero and non-finite
-// norms included), or a padding row.
+// norms included), or a padding row. row0 (a multiple of 256) is the first
+// row of the launch, here and in the three builders below: 0 for a whole
+// shadow, the block that holds the first new row after an in-place append.
 __global__ void k_shadow(const float *__restrict__ cm,
                          const double *__restrict__ norms,
                          uint16_t *__restrict__ sh, float *__restrict__ pinv,
                          uint64_t n, uint64_t n_pad, uint64_t sn_pad,
-                         uint32_t d) {
-	uint64_t r0 = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) *
-	              PF_ROWS_PER_LANE;
+                         uint32_t d, uint64_t row0) {
+	uint64_t r0 = row0 + ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) *
+	                         PF_ROWS_PER_LANE;
 	if (r0 >= sn_pad)
 		return;
 	const bool in_cm = r0 < n_pad; // n_pad % 8 == 0: a group is all in or out
@@ -1299,8 +1309,9 @@ __global__ void k_shadow_i8(const float *__restrict__ cm,
                             uint8_t *__restrict__ sh,
                             float *__restrict__ pscale,
                             float *__restrict__ peps, uint64_t n,
-                            uint64_t n_pad, uint64_t sn_pad, uint32_t d) {
-	const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+                            uint64_t n_pad, uint64_t sn_pad, uint32_t d,
+                            uint64_t row0) {
+	const uint64_t r = row0 + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
 	if (r >= sn_pad)
 		return;
 	float sc, ps = __uint_as_float(0x7FC00000u), pe = 0.f;
@@ -1520,8 +1531,8 @@ __global__ void k_shadow_l2(const float *__restrict__ cm,
                             uint8_t *__restrict__ sh, float *__restrict__ scale,
                             float *__restrict__ xx, float *__restrict__ res,
                             uint64_t n, uint64_t n_pad, uint64_t sn_pad,
-                            uint32_t d) {
-	const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+                            uint32_t d, uint64_t row0) {
+	const uint64_t r = row0 + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
 	if (r >= sn_pad)
 		return;
 	float sc = __uint_as_float(0x7FC00000u), x2 = 0.f, rs = 0.f;
@@ -1923,8 +1934,9 @@ __global__ void k_shadow_i6(const float *__restrict__ cm,
                             uint32_t *__restrict__ xsum,
                             float *__restrict__ peps4,
                             uint32_t *__restrict__ xsum_h, uint64_t n,
-                            uint64_t n_pad, uint64_t sn_pad, uint32_t d) {
-	const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+                            uint64_t n_pad, uint64_t sn_pad, uint32_t d,
+                            uint64_t row0) {
+	const uint64_t r = row0 + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
 	if (r >= sn_pad)
 		return;
 	const uint32_t G = (d + 31) / 32;
@@ -2813,6 +2825,128 @@ __global__ void k_aux(const float *__restrict__ cm,
 		uint32_t idx = atomicAdd(&hdr->n_unc, 1u);
 		if (idx < BATCH_UNC_CAP)
 			unc_rows[idx] = (uint32_t)r;
+	}
+}
+
+// ---------------------------------------------------------------------------
+// In-place append (sdbv_append_rows): rows [n, n + m) of a
+// table with spare capacity, in one launch what k_transpose, k_fill_ids,
+// k_norms and k_aux do for a whole table.
+// One wave per 64 absolute-aligned rows (block = one wave), lane = row; lanes
+// whose row lies outside [n, n + m) write nothing. The wave walks the
+// features in blocks of APP_FB: it loads the row-major block coalesced
+// (256 B per row) into an LDS tile of odd row length, reads it back
+// transposed and writes cm[k * n_pad + r], 64 consecutive floats per
+// feature. APP_FB is a multiple of 8, so k % 8 is the position in the block
+// and each lane carries the sum-of-squares chain of k_norms / k_aux in
+// registers: eight partials by k % 8 over the whole groups of 8, combined as
+// ((p0+p4)+(p1+p5)) + ((p2+p6)+(p3+p7)), then the d % 8 tail in sequence.
+// rm holds the m new rows row-major; ids their ids, or null for id_next +
+// (r - n). norms is null off cosine tables, aux / unc_rows / hdr are null
+// off cosine and euclidean ones. hdr is the table's own and is not reset:
+// its maximum and its count continue.
+// ---------------------------------------------------------------------------
+#define APP_FB 64
+__global__ __launch_bounds__(64) void k_append_rows(
+    const float *__restrict__ rm, const uint64_t *__restrict__ ids,
+    uint64_t id_next, float *__restrict__ cm, double *__restrict__ norms,
+    float *__restrict__ aux, uint64_t *__restrict__ ids_dev, uint64_t n,
+    uint64_t m, uint64_t n_pad, uint32_t d, int metric,
+    uint32_t *__restrict__ unc_rows, BatchAuxHdr *__restrict__ hdr) {
+	__shared__ float tile[64][APP_FB + 1];
+	const uint32_t lane = threadIdx.x;
+	const uint64_t base = (n / 64 + blockIdx.x) * 64; // first row of the wave
+	const uint64_t r = base + lane;
+	const bool mine = r >= n && r < n + m; // r < n_pad: the host checked
+	const uint32_t d8 = d & ~7u;
+	float p[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+	float tail[8] = {0, 0, 0, 0, 0, 0, 0, 0}; // x * x of the d % 8 tail
+	for (uint32_t kb = 0; kb < d; kb += APP_FB) {
+		const uint32_t k = kb + lane;
+		// eight rows' loads in flight before their LDS stores
+#pragma unroll 1
+		for (uint32_t i0 = 0; i0 < 64; i0 += 8) {
+			float v[8];
+#pragma unroll
+			for (uint32_t j = 0; j < 8; j++) {
+				const uint64_t ri = base + i0 + j;
+				v[j] = 0.0f;
+				if (ri >= n && ri < n + m && k < d)
+					v[j] = rm[(ri - n) * d + k];
+			}
+#pragma unroll
+			for (uint32_t j = 0; j < 8; j++)
+				tile[i0 + j][lane] = v[j];
+		}
+		__syncthreads();
+#pragma unroll
+		for (uint32_t g = 0; g < APP_FB; g += 8) {
+#pragma unroll
+			for (uint32_t j = 0; j < 8; j++) {
+				const uint32_t kk = kb + g + j;
+				const float x = tile[lane][g + j];
+				if (kk < d) {
+					if (mine)
+						cm[(uint64_t)kk * n_pad + r] = x;
+					const float xx = __fmul_rn(x, x);
+					if (kk < d8)
+						p[j] = __fadd_rn(p[j], xx);
+					else
+						tail[j] = xx;
+				}
+			}
+		}
+		__syncthreads();
+	}
+	if (!mine)
+		return;
+	ids_dev[r] = ids ? ids[r - n] : id_next + (r - n);
+	if (!norms && !aux)
+		return;
+	float acc = 0.0f;
+	acc = __fadd_rn(acc, __fadd_rn(__fadd_rn(p[0], p[4]), __fadd_rn(p[1], p[5])));
+	acc = __fadd_rn(acc, __fadd_rn(__fadd_rn(p[2], p[6]), __fadd_rn(p[3], p[7])));
+#pragma unroll
+	for (uint32_t j = 0; j < 8; j++)
+		if (d8 + j < d)
+			acc = __fadd_rn(acc, tail[j]);
+	const double norm = sqrt((double)acc);
+	if (norms)
+		norms[r] = norm;
+	if (!aux)
+		return;
+	// as k_aux: cosine 1 / norm, euclidean the sum of squares
+	const float a = metric == 0 ? (float)(1.0 / norm) : acc;
+	const bool covered =
+	    norm <= PF_NORM_MAX && (metric != 0 || norm >= PF_NORM_MIN);
+	if (covered) {
+		aux[r] = a;
+		atomicMax(&hdr->max_norm_bits,
+		          (unsigned long long)__double_as_longlong(norm));
+	} else {
+		aux[r] = __uint_as_float(0x7FC00000u);
+		uint32_t idx = atomicAdd(&hdr->n_unc, 1u);
+		if (idx < BATCH_UNC_CAP)
+			unc_rows[idx] = (uint32_t)r;
+	}
+}
+
+// Growth of a table's store: dst [d][new_pad] receives src [d][old_pad]
+// column by column and zeros in every cell at or past old_pad. Both strides
+// are multiples of 4, so a float4 never straddles a column or the old edge.
+__global__ void k_grow_cm(const float *__restrict__ src,
+                          float *__restrict__ dst, uint64_t old_pad,
+                          uint64_t new_pad, uint32_t d) {
+	const uint64_t q_new = new_pad / 4;
+	const uint64_t total = (uint64_t)d * q_new;
+	for (uint64_t idx = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	     idx < total; idx += (uint64_t)gridDim.x * blockDim.x) {
+		const uint64_t k = idx / q_new;
+		const uint64_t r = (idx % q_new) * 4;
+		float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+		if (r < old_pad)
+			v = *(const float4 *)(src + k * old_pad + r);
+		*(float4 *)(dst + k * new_pad + r) = v;
 	}
 }
 
@@ -4107,6 +4241,8 @@ void sdbv_shutdown(sdbv_ctx *ctx) {
 		(void)hipFree(ctx->sel_dev);
 	if (ctx->sel_pin)
 		(void)hipHostFree(ctx->sel_pin);
+	if (ctx->app_buf)
+		(void)hipFree(ctx->app_buf);
 	if (ctx->blas)
 		(void)rocblas_destroy_handle(ctx->blas);
 	(void)hipEventDestroy(ctx->ev0);
@@ -4210,6 +4346,51 @@ static uint64_t shadow_code_bytes(int kind, uint32_t d, uint64_t sn_pad) {
 // h4 (int6 only): with the H-only side data, 8 B per row more. Staging asks
 // for it when h4_policy holds; the explicit entries build the plain shadow,
 // also in place of a staged one that carries the side data.
+// Launch the shadow builder of t->sh over rows [row0, row_end), both
+// multiples of 256 with row_end <= sn_pad (the bf16 builder's last block may
+// run on to sn_pad, its own guard): the whole shadow when staging or growth
+// builds it, the 256-row blocks around the new rows after an in-place append.
+// A builder writes row r from cm alone, so writing a row again is idempotent.
+// n = the table's row count as the builders shall see it: an append passes
+// the count it is about to commit.
+static void launch_shadow_rows(sdbv_ctx *ctx, Table *t, uint64_t n,
+                               uint64_t row0, uint64_t row_end) {
+	const Shadow &sh = t->sh;
+	const uint64_t sn_pad = sh.sn_pad;
+	const uint64_t rows = row_end - row0;
+	if (rows == 0)
+		return;
+	switch (sh.kind) {
+	case 1: { // one lane per PF_ROWS_PER_LANE rows
+		uint64_t groups = rows / PF_ROWS_PER_LANE;
+		hipLaunchKernelGGL(k_shadow, dim3((uint32_t)((groups + 255) / 256)),
+		                   dim3(256), 0, ctx->stream, t->cm, t->norms,
+		                   (uint16_t *)sh.codes, sh.pinv(), n, t->n_pad,
+		                   sn_pad, t->d, row0);
+		break;
+	}
+	case 2: // one lane per row
+		hipLaunchKernelGGL(k_shadow_i8, dim3((uint32_t)(rows / 256)),
+		                   dim3(256), 0, ctx->stream, t->cm, t->norms,
+		                   (uint8_t *)sh.codes, sh.pscale(), sh.peps(), n,
+		                   t->n_pad, sn_pad, t->d, row0);
+		break;
+	case 3:
+		hipLaunchKernelGGL(k_shadow_i6, dim3((uint32_t)(rows / 256)),
+		                   dim3(256), 0, ctx->stream, t->cm, t->norms,
+		                   sh.plane_h(), sh.plane_l(t->d), sh.pscale(),
+		                   sh.peps(), sh.xsum(), sh.peps4(), sh.xsum_h(), n,
+		                   t->n_pad, sn_pad, t->d, row0);
+		break;
+	case 5: // one lane per row
+		hipLaunchKernelGGL(k_shadow_l2, dim3((uint32_t)(rows / 256)),
+		                   dim3(256), 0, ctx->stream, t->cm,
+		                   (uint8_t *)sh.codes, sh.pscale(), sh.l2_xx(),
+		                   sh.l2_res(), n, t->n_pad, sn_pad, t->d, row0);
+		break;
+	}
+}
+
 static int build_shadow(sdbv_ctx *ctx, Table *t, int kind, bool h4 = false) {
 	if (t->metric !=
 	    (kind == 5 ? SDBV_METRIC_EUCLIDEAN : SDBV_METRIC_COSINE))
@@ -4222,7 +4403,11 @@ static int build_shadow(sdbv_ctx *ctx, Table *t, int kind, bool h4 = false) {
 	const ShadowTier &tier = SHADOW_TIERS[kind];
 	Shadow sh;
 	sh.h4 = h4;
-	sh.sn_pad = ((t->n + tier.tile - 1) / tier.tile) * tier.tile;
+	// from the capacity, not from n: appended rows need their shadow cells.
+	// For a table as staged, n_pad = roundup(n, TILE) and every tier's tile is
+	// a multiple of TILE, so this is roundup(n, tile) as before; a grown
+	// capacity is a multiple of every tile, so sn_pad == n_pad.
+	sh.sn_pad = ((t->n_pad + tier.tile - 1) / tier.tile) * tier.tile;
 	if (sh.sn_pad == 0)
 		sh.sn_pad = tier.tile;
 	const uint64_t code_bytes = shadow_code_bytes(kind, t->d, sh.sn_pad);
@@ -4239,36 +4424,7 @@ static int build_shadow(sdbv_ctx *ctx, Table *t, int kind, bool h4 = false) {
 	sh.bytes = code_bytes + side_bytes;
 	t->sh = sh;
 	t->bytes += sh.bytes;
-	const uint64_t sn_pad = sh.sn_pad;
-	switch (kind) {
-	case 1: { // one lane per PF_ROWS_PER_LANE rows
-		uint64_t groups = sn_pad / PF_ROWS_PER_LANE;
-		hipLaunchKernelGGL(k_shadow, dim3((uint32_t)((groups + 255) / 256)),
-		                   dim3(256), 0, ctx->stream, t->cm, t->norms,
-		                   (uint16_t *)sh.codes, sh.pinv(), t->n, t->n_pad,
-		                   sn_pad, t->d);
-		break;
-	}
-	case 2: // one lane per row
-		hipLaunchKernelGGL(k_shadow_i8, dim3((uint32_t)(sn_pad / 256)),
-		                   dim3(256), 0, ctx->stream, t->cm, t->norms,
-		                   (uint8_t *)sh.codes, sh.pscale(), sh.peps(), t->n,
-		                   t->n_pad, sn_pad, t->d);
-		break;
-	case 3:
-		hipLaunchKernelGGL(k_shadow_i6, dim3((uint32_t)(sn_pad / 256)),
-		                   dim3(256), 0, ctx->stream, t->cm, t->norms,
-		                   sh.plane_h(), sh.plane_l(t->d), sh.pscale(),
-		                   sh.peps(), sh.xsum(), sh.peps4(), sh.xsum_h(), t->n,
-		                   t->n_pad, sn_pad, t->d);
-		break;
-	case 5: // one lane per row
-		hipLaunchKernelGGL(k_shadow_l2, dim3((uint32_t)(sn_pad / 256)),
-		                   dim3(256), 0, ctx->stream, t->cm,
-		                   (uint8_t *)sh.codes, sh.pscale(), sh.l2_xx(),
-		                   sh.l2_res(), t->n, t->n_pad, sn_pad, t->d);
-		break;
-	}
+	launch_shadow_rows(ctx, t, t->n, 0, sh.sn_pad);
 	HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
 	HIP_CHECK(ctx, hipGetLastError());
 	refresh_bytes_staged(ctx);
@@ -4402,6 +4558,8 @@ static int stage_corpus_impl(sdbv_ctx *ctx, uint64_t table, const float *rows,
 	int rc = stage_common(ctx, table, n, d, metric, &t);
 	if (rc != SDBV_OK)
 		return rc;
+	t->scan_table = scan_table;
+	t->last_id = n ? (ids ? ids[n - 1] : n - 1) : 0;
 	// upload row-major then transpose on device
 	float *rm = nullptr;
 	HIP_CHECK(ctx, hipMalloc(&rm, n * (uint64_t)d * sizeof(float)));
@@ -4620,6 +4778,7 @@ int sdbv_stage_synthetic(sdbv_ctx *ctx, uint64_t table, uint64_t n, uint32_t d,
 	int rc = stage_common(ctx, table, n, d, metric, &t);
 	if (rc != SDBV_OK)
 		return rc;
+	t->last_id = n ? id_base + n - 1 : 0;
 	hipLaunchKernelGGL(k_gen_cm, dim3(8192), dim3(256), 0, ctx->stream, t->cm,
 	                   t->n, t->n_pad, t->d, seed, row_offset);
 	uint64_t nb = (t->n_pad + THREADS - 1) / THREADS;
@@ -5588,12 +5747,18 @@ static bool filter_prefilter_policy(const Table &t) {
 
 // Upload the bitmap of the filtered call to ctx->flt_mask, once per call:
 // pinned copy, tail of the last word cleared, zero-filled behind it, one H2D
-// copy. The buffers hold max(n_pad, sn_pad) / 64 words: k_scan<., true>
-// reads words below n_pad / 64, the masked prefilter kernels address rows up
-// to the shadow's sn_pad >= n_pad.
+// copy. The buffers hold max(n_pad, sn_pad) / 64 words on a table as staged:
+// k_scan<., true> reads words below roundup(n, TILE) / 64, the masked
+// prefilter kernels address rows up to roundup(n, the tier's tile).
 static int upload_filter_mask(sdbv_ctx *ctx, const Table &t,
                               const uint64_t *allow, uint64_t allow_words) {
-	const uint64_t mwords = std::max(t.n_pad, t.sh.kind ? t.sh.sn_pad : 0) / 64;
+	// No kernel reads a mask word past the last tile that holds rows, and the
+	// largest tile (PF8_TILE) is 4096 rows: a capacity that reaches further
+	// (a table appended to or reserved) costs no words.
+	const uint64_t mwords =
+	    std::min(std::max(t.n_pad, t.sh.kind ? t.sh.sn_pad : 0),
+	             (t.n + 4095) / 4096 * 4096) /
+	    64;
 	if (ctx->flt_mask_cap < mwords) {
 		if (ctx->flt_mask)
 			(void)hipFree(ctx->flt_mask);
@@ -5864,6 +6029,228 @@ static int ensure_cap(sdbv_ctx *ctx, void **buf, uint64_t *cap, uint64_t need) {
 	return SDBV_OK;
 }
 
+// ---------------------------------------------------------------------------
+// Appending rows to a staged table
+// ---------------------------------------------------------------------------
+// Capacities grow to multiples of this: the least common multiple of TILE
+// and the shadow tiers' tiles, so a grown table has sn_pad == n_pad.
+#define APPEND_CAP_ALIGN 4096ull
+static_assert(APPEND_CAP_ALIGN % TILE == 0 && APPEND_CAP_ALIGN % PF_TILE == 0 &&
+                  APPEND_CAP_ALIGN % PF8_TILE == 0 &&
+                  APPEND_CAP_ALIGN % PF6_TILE == 0,
+              "a grown capacity must be whole tiles on every tier");
+// Rows of one append go through the context's staging buffer in chunks of
+// at most this many bytes.
+#define APPEND_CHUNK_BYTES (256ull << 20)
+
+uint64_t sdbv_append_capacity(uint64_t n_pad, uint64_t need) {
+	if (need <= n_pad)
+		return n_pad;
+	const uint64_t want = std::max(need, n_pad + n_pad / 2);
+	return (want + APPEND_CAP_ALIGN - 1) / APPEND_CAP_ALIGN * APPEND_CAP_ALIGN;
+}
+
+// Device bytes of a table's per-row arrays at capacity cap, as staging
+// counts them (the shadow and the fixed 4 KiB of bunc aside).
+static uint64_t table_store_bytes(const Table &t, uint64_t cap) {
+	uint64_t b = (uint64_t)t.d * cap * sizeof(float) + cap * sizeof(uint64_t);
+	if (t.norms)
+		b += cap * sizeof(double);
+	if (t.aux)
+		b += cap * sizeof(float);
+	return b;
+}
+
+// Regrow a table's store to new_cap > n_pad rows (a multiple of
+// APPEND_CAP_ALIGN). The new arrays are allocated before the old ones are
+// freed, so a failed allocation leaves the table as it was (SDBV_ERR_OOM) and
+// the peak is old plus new. cm is copied column by column at the new stride
+// with zeros behind the old stride; the per-row arrays keep their first n
+// entries. A shadow is rebuilt at the new capacity, same kind and side data;
+// one that no longer fits is dropped and the table goes on without.
+static int grow_table(sdbv_ctx *ctx, Table *t, uint64_t new_cap) {
+	float *cm = nullptr, *aux = nullptr;
+	double *norms = nullptr;
+	uint64_t *ids = nullptr;
+	const bool ok =
+	    hipMalloc(&cm, (uint64_t)t->d * new_cap * sizeof(float)) == hipSuccess &&
+	    (!t->norms ||
+	     hipMalloc(&norms, new_cap * sizeof(double)) == hipSuccess) &&
+	    (!t->aux || hipMalloc(&aux, new_cap * sizeof(float)) == hipSuccess) &&
+	    hipMalloc(&ids, new_cap * sizeof(uint64_t)) == hipSuccess;
+	auto free_new = [&]() {
+		for (void *p : {(void *)cm, (void *)norms, (void *)aux, (void *)ids})
+			if (p)
+				(void)hipFree(p);
+	};
+	if (!ok) {
+		(void)hipGetLastError(); // allocation failure is not sticky
+		free_new();
+		ctx->err = "grow_table: allocation failed";
+		return SDBV_ERR_OOM;
+	}
+	hipLaunchKernelGGL(k_grow_cm, dim3(8192), dim3(256), 0, ctx->stream, t->cm,
+	                   cm, t->n_pad, new_cap, t->d);
+	hipError_t e = hipSuccess;
+	if (t->n) {
+		if (norms)
+			e = hipMemcpyAsync(norms, t->norms, t->n * sizeof(double),
+			                   hipMemcpyDeviceToDevice, ctx->stream);
+		if (aux && e == hipSuccess)
+			e = hipMemcpyAsync(aux, t->aux, t->n * sizeof(float),
+			                   hipMemcpyDeviceToDevice, ctx->stream);
+		if (e == hipSuccess)
+			e = hipMemcpyAsync(ids, t->ids_dev, t->n * sizeof(uint64_t),
+			                   hipMemcpyDeviceToDevice, ctx->stream);
+	}
+	if (e == hipSuccess)
+		e = hipStreamSynchronize(ctx->stream);
+	if (e == hipSuccess)
+		e = hipGetLastError();
+	if (e != hipSuccess) {
+		free_new();
+		ctx->err = std::string("grow_table: ") + hipGetErrorString(e);
+		return SDBV_ERR_HIP;
+	}
+	(void)hipFree(t->cm);
+	if (t->norms)
+		(void)hipFree(t->norms);
+	if (t->aux)
+		(void)hipFree(t->aux);
+	(void)hipFree(t->ids_dev);
+	t->cm = cm;
+	t->norms = norms;
+	t->aux = aux;
+	t->ids_dev = ids;
+	t->n_pad = new_cap;
+	t->bytes = table_store_bytes(*t, new_cap) + t->sh.bytes;
+	refresh_bytes_staged(ctx);
+	if (t->sh.kind) {
+		const int kind = t->sh.kind;
+		const bool h4 = t->sh.h4;
+		free_shadow(ctx, t);
+		int rc = build_shadow(ctx, t, kind, h4);
+		if (rc != SDBV_OK && rc != SDBV_ERR_OOM)
+			return rc;
+	}
+	return SDBV_OK;
+}
+
+uint64_t sdbv_table_capacity(sdbv_ctx *ctx, uint64_t table) {
+	std::lock_guard<std::mutex> lk(ctx->mu);
+	auto it = ctx->tables.find(table);
+	return it == ctx->tables.end() ? 0 : it->second.n_pad;
+}
+
+int sdbv_table_reserve(sdbv_ctx *ctx, uint64_t table, uint64_t rows) {
+	std::lock_guard<std::mutex> lk(ctx->mu);
+	auto it = ctx->tables.find(table);
+	if (it == ctx->tables.end())
+		return SDBV_ERR_NO_TABLE;
+	Table *t = &it->second;
+	if (!t->scan_table)
+		return SDBV_ERR_UNSUPPORTED;
+	if (rows <= t->n_pad)
+		return SDBV_OK;
+	if (rows >= (1ULL << 32))
+		return SDBV_ERR_BAD_ARG;
+	return grow_table(ctx, t, (rows + APPEND_CAP_ALIGN - 1) / APPEND_CAP_ALIGN *
+	                              APPEND_CAP_ALIGN);
+}
+
+int sdbv_append_rows(sdbv_ctx *ctx, uint64_t table, const float *rows,
+                     const uint64_t *ids, uint64_t m, uint32_t d) {
+	auto t_start = std::chrono::steady_clock::now();
+	std::lock_guard<std::mutex> lk(ctx->mu);
+	auto it = ctx->tables.find(table);
+	if (it == ctx->tables.end())
+		return SDBV_ERR_NO_TABLE;
+	Table *t = &it->second;
+	if (!t->scan_table)
+		return SDBV_ERR_UNSUPPORTED;
+	if (d != t->d)
+		return SDBV_ERR_BAD_ARG;
+	if (m == 0)
+		return SDBV_OK;
+	if (!rows || m >= (1ULL << 32) || t->n + m >= (1ULL << 32))
+		return SDBV_ERR_BAD_ARG;
+	// tie-break contract: the ids of the whole table stay strictly increasing
+	if (ids) {
+		if (t->n && ids[0] <= t->last_id)
+			return SDBV_ERR_IDS_UNSORTED;
+		for (uint64_t i = 1; i < m; i++)
+			if (ids[i] <= ids[i - 1])
+				return SDBV_ERR_IDS_UNSORTED;
+	}
+	const uint64_t id_next = t->n ? t->last_id + 1 : 0;
+
+	const uint64_t cap = sdbv_append_capacity(t->n_pad, t->n + m);
+	const bool regrow = cap != t->n_pad;
+	if (regrow) {
+		int rc = grow_table(ctx, t, cap);
+		if (rc != SDBV_OK)
+			return rc;
+	}
+
+	const uint64_t row_bytes = (uint64_t)d * sizeof(float);
+	const uint64_t chunk_rows =
+	    std::max<uint64_t>(1, APPEND_CHUNK_BYTES / row_bytes);
+	int rc = ensure_cap(ctx, &ctx->app_buf, &ctx->app_buf_cap,
+	                    std::min(m, chunk_rows) *
+	                        (row_bytes + sizeof(uint64_t)));
+	if (rc != SDBV_OK)
+		return rc;
+	BatchAuxHdr *hdr =
+	    t->bunc ? (BatchAuxHdr *)(t->bunc + BATCH_UNC_CAP) : nullptr;
+	double kernel_ms = 0;
+	for (uint64_t done = 0; done < m;) {
+		const uint64_t c = std::min(chunk_rows, m - done);
+		// d % 4 == 0: the ids behind the rows are 8-byte aligned
+		float *rm = (float *)ctx->app_buf;
+		uint64_t *idb = (uint64_t *)((char *)ctx->app_buf + c * row_bytes);
+		HIP_CHECK(ctx, hipMemcpyAsync(rm, rows + done * d, c * row_bytes,
+		                              hipMemcpyHostToDevice, ctx->stream));
+		if (ids)
+			HIP_CHECK(ctx, hipMemcpyAsync(idb, ids + done, c * sizeof(uint64_t),
+			                              hipMemcpyHostToDevice, ctx->stream));
+		const uint64_t n0 = t->n + done; // n0 + c <= n_pad
+		const uint64_t waves = (n0 + c + 63) / 64 - n0 / 64;
+		HIP_CHECK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+		hipLaunchKernelGGL(k_append_rows, dim3((uint32_t)waves), dim3(64), 0,
+		                   ctx->stream, rm, ids ? idb : (const uint64_t *)nullptr,
+		                   id_next + done, t->cm, t->norms, t->aux, t->ids_dev,
+		                   n0, c, t->n_pad, d, (int)t->metric, t->bunc, hdr);
+		done += c;
+		if (done == m && t->sh.kind) {
+			// the 256-row blocks that hold [n, n + m): the new rows get their
+			// codes, rows that stop being padding lose their NaN side value
+			const uint64_t end = (t->n + m + 255) / 256 * 256;
+			launch_shadow_rows(ctx, t, t->n + m, t->n / 256 * 256, end);
+		}
+		HIP_CHECK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+		HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+		HIP_CHECK(ctx, hipGetLastError());
+		float ms = 0;
+		(void)hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1);
+		kernel_ms += ms;
+	}
+	if (hdr) { // as finish_stage reads them
+		BatchAuxHdr h;
+		HIP_CHECK(ctx, hipMemcpy(&h, hdr, sizeof(h), hipMemcpyDeviceToHost));
+		t->bunc_n = h.n_unc;
+		std::memcpy(&t->bmax_norm, &h.max_norm_bits, sizeof(double));
+	}
+	t->last_id = ids ? ids[m - 1] : id_next + m - 1;
+	t->n += m;
+	ctx->stats.last_append_kernel_ms = kernel_ms;
+	ctx->stats.last_append_realloc = regrow ? 1u : 0u;
+	ctx->stats.last_append_ms =
+	    std::chrono::duration<double, std::milli>(
+	        std::chrono::steady_clock::now() - t_start)
+	        .count();
+	return SDBV_OK;
+}
+
 int sdbv_knn_batch(sdbv_ctx *ctx, uint64_t table, const float *Q, uint32_t b,
                    uint32_t d, uint32_t k, uint64_t *out_ids,
                    double *out_dists) {
@@ -5931,9 +6318,12 @@ int sdbv_knn_batch(sdbv_ctx *ctx, uint64_t table, const float *Q, uint32_t b,
 	}
 
 	// chunk size: multiple of TILE, bounded scratch (<=1 GiB at b=1024)
+	// (n_tile, not n_pad: the capacity of a table that was appended to or
+	// reserved reaches past the last tile that holds rows)
+	const uint64_t n_tile = (t.n + TILE - 1) / TILE * TILE;
 	uint64_t chunk = 262144;
-	if (chunk > t.n_pad)
-		chunk = t.n_pad;
+	if (chunk > n_tile)
+		chunk = n_tile;
 	int rc;
 	if ((rc = ensure_cap(ctx, (void **)&ctx->S, &ctx->S_cap,
 	                     chunk * b * sizeof(float))))
@@ -5984,7 +6374,7 @@ int sdbv_knn_batch(sdbv_ctx *ctx, uint64_t table, const float *Q, uint32_t b,
 		// guard skips them); a bounded `to` (the TILE-aligned bootstrap)
 		// is covered exactly.
 		for (uint64_t row0 = from; row0 < to; row0 += chunk) {
-			uint64_t lim = (to == t.n) ? t.n_pad : to;
+			uint64_t lim = (to == t.n) ? n_tile : to;
 			uint32_t nc = (uint32_t)std::min<uint64_t>(chunk, lim - row0);
 			const float alpha = 1.0f, beta = 0.0f;
 			HIP_CHECK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
@@ -6121,10 +6511,9 @@ int sdbv_knn_batch(sdbv_ctx *ctx, uint64_t table, const float *Q, uint32_t b,
 	}
 
 	// final exact rank per query: ascending (total_cmp(dist), id)
-	std::vector<uint64_t> ids_host(t.n_pad);
+	std::vector<uint64_t> ids_host(t.n);
 	HIP_CHECK(ctx, hipMemcpy(ids_host.data(), t.ids_dev,
-	                         t.n_pad * sizeof(uint64_t),
-	                         hipMemcpyDeviceToHost));
+	                         t.n * sizeof(uint64_t), hipMemcpyDeviceToHost));
 	auto total_key = [](double x) {
 		uint64_t bits;
 		std::memcpy(&bits, &x, 8);
