@@ -146,6 +146,13 @@ typedef struct sdbv_stats {
 	                                 not in it) */
 	uint32_t last_append_realloc; /* 0 if that call wrote in place, 1 if it
 	                                 regrew the table's store first */
+	double last_update_ms;        /* host wall of the last sdbv_update_rows call
+	                                 that changed rows, its synchronisation
+	                                 included */
+	double last_update_kernel_ms; /* HIP-event time of that call's scatter
+	                                 kernel, shadow update and header refold */
+	uint64_t last_update_blocks;  /* 256-row shadow blocks that call rewrote
+	                                 (0 on a table without a shadow) */
 } sdbv_stats;
 
 /* Create a context on HIP device `device` (-1 = current device). */
@@ -163,7 +170,8 @@ int sdbv_get_stats(sdbv_ctx *, sdbv_stats *out);
  * (distance asc, id asc), which equals the reference's orderings for
  * monotone ids (knn.rs:363 BTreeSet<(FloatKey, VectorId)>, knn_topk.rs:61-73
  * insertion-order seq). Restages (replaces) if `table` already staged;
- * sdbv_append_rows adds rows behind the staged ones without restaging.
+ * sdbv_append_rows adds rows behind the staged ones without restaging,
+ * sdbv_update_rows replaces the vectors of staged rows.
  *
  * Memory: d*4 + 20 B per row. A COSINE table of at least
  * SDBV_SCAN_PREFILTER_MIN_ROWS rows (environment, default 500000) also gets
@@ -311,8 +319,8 @@ int sdbv_drop_table(sdbv_ctx *, uint64_t table);
  * sdbv_stage_synthetic, without restaging it. `ids` must be strictly
  * increasing with ids[0] above the table's last staged id (NULL => last id
  * + 1, + 2, ...), which keeps the tie-break contract of sdbv_stage_corpus. A
- * row whose id sorts INSIDE the staged range, and a change to a staged row,
- * still need a restage. After SDBV_OK every search entry point answers in
+ * row whose id sorts INSIDE the staged range still needs a restage; a change
+ * to a staged row is sdbv_update_rows. After SDBV_OK every search entry point answers in
  * every bit (ids, distance bits, *out_n, and the path and candidate counts
  * of sdbv_stats) as if the table had been staged once with the concatenated
  * rows and ids. Synchronous; holds the context mutex.
@@ -342,6 +350,40 @@ int sdbv_drop_table(sdbv_ctx *, uint64_t table);
  * regrowth is SDBV_ERR_OOM with the table intact. */
 int sdbv_append_rows(sdbv_ctx *, uint64_t table, const float *rows,
                      const uint64_t *ids, uint64_t m, uint32_t d);
+/* Replace the vectors of m staged rows in place, without restaging the
+ * table. `row_idx` holds m row POSITIONS, strictly increasing and all < n
+ * (the convention of sdbv_knn_bruteforce_filtered and sdbv_gather_distance:
+ * ids are increasing, so the position of a record is the rank of its id);
+ * `rows` is m x d row-major, row i replaces the vector at position
+ * row_idx[i]. Ids, n, the capacity and bytes_staged do not change, and the
+ * call allocates nothing once the context's staging buffer is large enough
+ * (rows and their positions pass through it in chunks of at most 256 MiB):
+ * there is never a regrowth. After SDBV_OK every search entry point answers
+ * in every bit (ids, distance bits, *out_n, and the path and candidate
+ * counts of sdbv_stats) as if the table had been staged once with the
+ * current rows and ids and the same shadow kind and side data. A table keeps
+ * the shadow it has. Synchronous; holds the context mutex.
+ *
+ * One kernel scatters the rows into the feature-major store and writes their
+ * norms and batch aux; the table's prefilter shadow is rebuilt over exactly
+ * the distinct 256-row blocks that hold a listed row (sdbv_update_blocks, one
+ * launch); on cosine and euclidean tables the batch path's largest keyed norm
+ * and its rows without a usable key are then recomputed from the per-row
+ * arrays (4-12 B per row), since an overwritten row must be forgotten.
+ *
+ * Checked before anything is touched (a refused call leaves the table as it
+ * was): SDBV_ERR_NO_TABLE; SDBV_ERR_UNSUPPORTED for a table staged for graph
+ * search; SDBV_ERR_BAD_ARG when d differs from the table's, rows or row_idx
+ * is NULL with m > 0, a position is >= n, or the positions are not strictly
+ * increasing (so no position occurs twice). m == 0 is SDBV_OK and nothing
+ * happens. */
+int sdbv_update_rows(sdbv_ctx *, uint64_t table, const uint32_t *row_idx,
+                     const float *rows, uint64_t m, uint32_t d);
+/* Host-only: the distinct 256-row blocks (row / 256) that hold the m strictly
+ * increasing positions, ascending; returns their number and writes the first
+ * min(count, cap) to out_blocks (may be NULL with cap 0). */
+uint64_t sdbv_update_blocks(const uint32_t *row_idx, uint64_t m,
+                            uint32_t *out_blocks, uint64_t cap);
 /* Grow the table's capacity to at least `rows` now (rounded up to a multiple
  * of 4096, no growth factor), as a regrowing append does; a no-op when the
  * capacity is already that large. A bulk loader reserves once and then

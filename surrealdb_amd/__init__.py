@@ -72,6 +72,18 @@ class _Stats(ctypes.Structure):
     ]
 
 
+class _StatsUpdate(_Stats):
+    """sdbv_stats as it is now: the layout above, which
+    tests/test_append_capacity.py pins as ending with the append fields, and
+    behind it the fields of sdbv_update_rows. This is the structure
+    sdbv_get_stats fills."""
+    _fields_ = [
+        ("last_update_ms", ctypes.c_double),
+        ("last_update_kernel_ms", ctypes.c_double),
+        ("last_update_blocks", ctypes.c_uint64),
+    ]
+
+
 _lib = None
 
 
@@ -96,13 +108,16 @@ def lib():
     L.sdbv_shutdown.argtypes = [vp]
     L.sdbv_last_error.restype = ctypes.c_char_p
     L.sdbv_last_error.argtypes = [vp]
-    L.sdbv_get_stats.argtypes = [vp, ctypes.POINTER(_Stats)]
+    L.sdbv_get_stats.argtypes = [vp, ctypes.POINTER(_StatsUpdate)]
     L.sdbv_stage_corpus.argtypes = [vp, u64, f32p, u64p, u64, u32, u8]
     L.sdbv_stage_synthetic.argtypes = [vp, u64, u64, u32, u8, u64, u64, u64]
     L.sdbv_table_rows.restype = u64
     L.sdbv_table_rows.argtypes = [vp, u64]
     L.sdbv_drop_table.argtypes = [vp, u64]
     L.sdbv_append_rows.argtypes = [vp, u64, f32p, u64p, u64, u32]
+    L.sdbv_update_rows.argtypes = [vp, u64, u32p, f32p, u64, u32]
+    L.sdbv_update_blocks.restype = u64
+    L.sdbv_update_blocks.argtypes = [u32p, u64, u32p, u64]
     L.sdbv_table_reserve.argtypes = [vp, u64, u64]
     L.sdbv_table_capacity.restype = u64
     L.sdbv_table_capacity.argtypes = [vp, u64]
@@ -259,10 +274,11 @@ class Context:
             pass
 
     def stats(self):
-        s = _Stats()
+        s = _StatsUpdate()
         _check(self._ptr, lib().sdbv_get_stats(self._ptr, ctypes.byref(s)),
                "sdbv_get_stats")
-        return {f: getattr(s, f) for f, _ in s._fields_}
+        return {f: getattr(s, f)
+                for f, _ in _Stats._fields_ + _StatsUpdate._fields_}
 
     def stage_corpus(self, table, rows, ids=None, metric="cosine",
                      order=None):
@@ -318,6 +334,30 @@ class Context:
             self._ptr, table,
             rows.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), idp, m, d),
             "sdbv_append_rows")
+
+    def update_rows(self, table, row_idx, rows):
+        """Replace the vectors at the row positions row_idx (strictly
+        increasing, all below table_rows) of a staged scan table by the rows
+        of an (m, d) array, without restaging it. Ids, row count and capacity
+        stay. Afterwards every search answers in every bit as if the table
+        had been staged once with the current rows (stats last_update_ms /
+        last_update_kernel_ms say what it cost, last_update_blocks how many
+        256-row shadow blocks were rewritten)."""
+        import numpy as np
+        rows = np.ascontiguousarray(rows, dtype=np.float32)
+        if rows.ndim != 2:
+            raise SdbvError(f"update_rows: (m, d) array expected, got "
+                            f"shape {rows.shape}")
+        m, d = rows.shape
+        row_idx = np.ascontiguousarray(row_idx, dtype=np.uint32)
+        if row_idx.shape != (m,):
+            raise SdbvError(f"update_rows: {row_idx.size} positions for "
+                            f"{m} rows")
+        _check(self._ptr, lib().sdbv_update_rows(
+            self._ptr, table,
+            row_idx.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
+            rows.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), m, d),
+            "sdbv_update_rows")
 
     def table_reserve(self, table, rows):
         """Grow the table's capacity to at least `rows` (rounded up to a
@@ -522,6 +562,21 @@ def select_topk(dists, k, allow=None):
     if rc != 0:
         raise SdbvError(f"sdbv_select_topk failed ({rc})")
     return rows[:out_n.value]
+
+
+def update_blocks(row_idx):
+    """Host-only: the distinct 256-row blocks (row // 256), ascending, that
+    hold the strictly increasing row positions row_idx -- the blocks of the
+    prefilter shadow that Context.update_rows rewrites."""
+    import numpy as np
+    row_idx = np.ascontiguousarray(row_idx, dtype=np.uint32)
+    u32p = ctypes.POINTER(ctypes.c_uint32)
+    count = lib().sdbv_update_blocks(row_idx.ctypes.data_as(u32p),
+                                     row_idx.size, None, 0)
+    out = np.empty(count, dtype=np.uint32)
+    lib().sdbv_update_blocks(row_idx.ctypes.data_as(u32p), row_idx.size,
+                             out.ctypes.data_as(u32p), count)
+    return out
 
 
 def append_capacity(n_pad, need):

@@ -933,13 +933,24 @@ __device__ static inline float d_unkey32(uint32_t k) {
 // norms included), or a padding row. row0 (a multiple of 256) is the first
 // row of the launch, here and in the three builders below: 0 for a whole
 // shadow, the block that holds the first new row after an in-place append.
+// blist, when not null, lists 256-row blocks (row / 256, sdbv_update_rows)
+// and replaces the contiguous range: workgroup j of the three builders below
+// works on block blist[j], and here lane group j of n_list does.
 __global__ void k_shadow(const float *__restrict__ cm,
                          const double *__restrict__ norms,
                          uint16_t *__restrict__ sh, float *__restrict__ pinv,
                          uint64_t n, uint64_t n_pad, uint64_t sn_pad,
-                         uint32_t d, uint64_t row0) {
-	uint64_t r0 = row0 + ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) *
-	                         PF_ROWS_PER_LANE;
+                         uint32_t d, uint64_t row0,
+                         const uint32_t *__restrict__ blist, uint32_t n_list) {
+	const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	uint64_t r0 = row0 + g * PF_ROWS_PER_LANE;
+	if (blist) { // 256 / PF_ROWS_PER_LANE lanes per listed block
+		const uint64_t j = g / (256 / PF_ROWS_PER_LANE);
+		if (j >= n_list)
+			return;
+		r0 = (uint64_t)blist[j] * 256 +
+		     g % (256 / PF_ROWS_PER_LANE) * PF_ROWS_PER_LANE;
+	}
 	if (r0 >= sn_pad)
 		return;
 	const bool in_cm = r0 < n_pad; // n_pad % 8 == 0: a group is all in or out
@@ -1310,8 +1321,11 @@ __global__ void k_shadow_i8(const float *__restrict__ cm,
                             float *__restrict__ pscale,
                             float *__restrict__ peps, uint64_t n,
                             uint64_t n_pad, uint64_t sn_pad, uint32_t d,
-                            uint64_t row0) {
-	const uint64_t r = row0 + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+                            uint64_t row0,
+                            const uint32_t *__restrict__ blist) {
+	const uint64_t r = (blist ? (uint64_t)blist[blockIdx.x] * 256
+	                          : row0 + (uint64_t)blockIdx.x * blockDim.x) +
+	                   threadIdx.x;
 	if (r >= sn_pad)
 		return;
 	float sc, ps = __uint_as_float(0x7FC00000u), pe = 0.f;
@@ -1531,8 +1545,11 @@ __global__ void k_shadow_l2(const float *__restrict__ cm,
                             uint8_t *__restrict__ sh, float *__restrict__ scale,
                             float *__restrict__ xx, float *__restrict__ res,
                             uint64_t n, uint64_t n_pad, uint64_t sn_pad,
-                            uint32_t d, uint64_t row0) {
-	const uint64_t r = row0 + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+                            uint32_t d, uint64_t row0,
+                            const uint32_t *__restrict__ blist) {
+	const uint64_t r = (blist ? (uint64_t)blist[blockIdx.x] * 256
+	                          : row0 + (uint64_t)blockIdx.x * blockDim.x) +
+	                   threadIdx.x;
 	if (r >= sn_pad)
 		return;
 	float sc = __uint_as_float(0x7FC00000u), x2 = 0.f, rs = 0.f;
@@ -1935,8 +1952,11 @@ __global__ void k_shadow_i6(const float *__restrict__ cm,
                             float *__restrict__ peps4,
                             uint32_t *__restrict__ xsum_h, uint64_t n,
                             uint64_t n_pad, uint64_t sn_pad, uint32_t d,
-                            uint64_t row0) {
-	const uint64_t r = row0 + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+                            uint64_t row0,
+                            const uint32_t *__restrict__ blist) {
+	const uint64_t r = (blist ? (uint64_t)blist[blockIdx.x] * 256
+	                          : row0 + (uint64_t)blockIdx.x * blockDim.x) +
+	                   threadIdx.x;
 	if (r >= sn_pad)
 		return;
 	const uint32_t G = (d + 31) / 32;
@@ -2928,6 +2948,148 @@ __global__ __launch_bounds__(64) void k_append_rows(
 		uint32_t idx = atomicAdd(&hdr->n_unc, 1u);
 		if (idx < BATCH_UNC_CAP)
 			unc_rows[idx] = (uint32_t)r;
+	}
+}
+
+// ---------------------------------------------------------------------------
+// In-place update (sdbv_update_rows): the scatter sibling of
+// k_append_rows. One wave per 64 consecutive entries of the row list, lane =
+// entry i, target row idx[i] (strictly increasing, all < n: the host
+// checked, so no two lanes write the same row). rm holds the m new rows
+// row-major. The loads are those of the append; the stores of a feature go
+// to cm[k * n_pad + idx[i]], scattered unless the listed rows are adjacent.
+// norms[row] and aux[row] are written as k_norms / k_aux would (aux NaN for
+// a row without a usable key); the batch header, the list of such rows and
+// the ids are not touched: k_aux_refold recomputes the first two.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void k_update_rows(
+    const float *__restrict__ rm, const uint32_t *__restrict__ idx,
+    float *__restrict__ cm, double *__restrict__ norms,
+    float *__restrict__ aux, uint64_t m, uint64_t n_pad, uint32_t d,
+    int metric) {
+	__shared__ float tile[64][APP_FB + 1];
+	const uint32_t lane = threadIdx.x;
+	const uint64_t base = (uint64_t)blockIdx.x * 64; // first entry of the wave
+	const bool mine = base + lane < m;
+	const uint64_t r = mine ? idx[base + lane] : 0;
+	const uint32_t d8 = d & ~7u;
+	float p[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+	float tail[8] = {0, 0, 0, 0, 0, 0, 0, 0}; // x * x of the d % 8 tail
+	for (uint32_t kb = 0; kb < d; kb += APP_FB) {
+		const uint32_t k = kb + lane;
+		// eight rows' loads in flight before their LDS stores
+#pragma unroll 1
+		for (uint32_t i0 = 0; i0 < 64; i0 += 8) {
+			float v[8];
+#pragma unroll
+			for (uint32_t j = 0; j < 8; j++) {
+				const uint64_t si = base + i0 + j;
+				v[j] = 0.0f;
+				if (si < m && k < d)
+					v[j] = rm[si * d + k];
+			}
+#pragma unroll
+			for (uint32_t j = 0; j < 8; j++)
+				tile[i0 + j][lane] = v[j];
+		}
+		__syncthreads();
+#pragma unroll
+		for (uint32_t g = 0; g < APP_FB; g += 8) {
+#pragma unroll
+			for (uint32_t j = 0; j < 8; j++) {
+				const uint32_t kk = kb + g + j;
+				const float x = tile[lane][g + j];
+				if (kk < d) {
+					if (mine)
+						cm[(uint64_t)kk * n_pad + r] = x;
+					const float xx = __fmul_rn(x, x);
+					if (kk < d8)
+						p[j] = __fadd_rn(p[j], xx);
+					else
+						tail[j] = xx;
+				}
+			}
+		}
+		__syncthreads();
+	}
+	if (!mine || (!norms && !aux))
+		return;
+	float acc = 0.0f;
+	acc = __fadd_rn(acc, __fadd_rn(__fadd_rn(p[0], p[4]), __fadd_rn(p[1], p[5])));
+	acc = __fadd_rn(acc, __fadd_rn(__fadd_rn(p[2], p[6]), __fadd_rn(p[3], p[7])));
+#pragma unroll
+	for (uint32_t j = 0; j < 8; j++)
+		if (d8 + j < d)
+			acc = __fadd_rn(acc, tail[j]);
+	const double norm = sqrt((double)acc);
+	if (norms)
+		norms[r] = norm;
+	if (!aux)
+		return;
+	// as k_aux: cosine 1 / norm, euclidean the sum of squares
+	const float a = metric == 0 ? (float)(1.0 / norm) : acc;
+	const bool covered =
+	    norm <= PF_NORM_MAX && (metric != 0 || norm >= PF_NORM_MIN);
+	aux[r] = covered ? a : __uint_as_float(0x7FC00000u);
+}
+
+// The batch header from the arrays (sdbv_update_rows): over aux[0..n), a row
+// with NaN aux is counted and listed in unc_rows while the count is below
+// BATCH_UNC_CAP, every other row gives its norm to the maximum -- norms[r] on
+// a cosine table, sqrt((double)aux[r]) on a euclidean one, the value k_aux
+// had. hdr is zero on entry. A wave reduces first: one atomicAdd for its
+// rows without a key, whose lanes take consecutive slots; the maximum goes
+// wave, then workgroup, then one atomicMax per workgroup when it leaves.
+// Grid-stride: at most this many workgroups, four per compute unit of a
+// 256-unit device, so a table whose rows all have a key issues at most 1024
+// atomics to the one address.
+#define REFOLD_MAX_BLOCKS 1024u
+__global__ __launch_bounds__(THREADS) void k_aux_refold(
+    const float *__restrict__ aux, const double *__restrict__ norms,
+    uint64_t n, uint32_t *__restrict__ unc_rows,
+    BatchAuxHdr *__restrict__ hdr) {
+	__shared__ unsigned long long wave_best[THREADS / 64];
+	const uint32_t lane = threadIdx.x & 63;
+	unsigned long long best = 0;
+	// the loop bound is the wave's first row: all 64 lanes stay together
+	for (uint64_t r0 = (uint64_t)blockIdx.x * THREADS + (threadIdx.x & ~63u);
+	     r0 < n; r0 += (uint64_t)gridDim.x * THREADS) {
+		const uint64_t r = r0 + lane;
+		bool unc = false;
+		if (r < n) {
+			const float a = aux[r];
+			unc = a != a;
+			if (!unc) {
+				const double norm = norms ? norms[r] : sqrt((double)a);
+				const unsigned long long b =
+				    (unsigned long long)__double_as_longlong(norm);
+				best = b > best ? b : best;
+			}
+		}
+		const unsigned long long vote = __ballot(unc);
+		if (vote) {
+			const int leader = __ffsll((long long)vote) - 1;
+			uint32_t slot = 0;
+			if ((int)lane == leader)
+				slot = atomicAdd(&hdr->n_unc, (uint32_t)__popcll(vote));
+			slot = __shfl(slot, leader);
+			slot += (uint32_t)__popcll(vote & ((1ull << lane) - 1));
+			if (unc && slot < BATCH_UNC_CAP)
+				unc_rows[slot] = (uint32_t)r;
+		}
+	}
+	for (int off = 32; off > 0; off >>= 1) {
+		const unsigned long long o = __shfl_down(best, off);
+		best = o > best ? o : best;
+	}
+	if (lane == 0)
+		wave_best[threadIdx.x >> 6] = best;
+	__syncthreads();
+	if (threadIdx.x == 0) {
+		for (uint32_t w = 1; w < THREADS / 64; w++)
+			best = wave_best[w] > best ? wave_best[w] : best;
+		if (best)
+			atomicMax(&hdr->max_norm_bits, best);
 	}
 }
 
@@ -4346,6 +4508,47 @@ static uint64_t shadow_code_bytes(int kind, uint32_t d, uint64_t sn_pad) {
 // h4 (int6 only): with the H-only side data, 8 B per row more. Staging asks
 // for it when h4_policy holds; the explicit entries build the plain shadow,
 // also in place of a staged one that carries the side data.
+// The builder of t->sh over nb 256-row blocks in one launch: those from row0
+// on (blist null), or the blocks blist[0..nb) on the device, ascending and
+// distinct (sdbv_update_rows).
+static void launch_shadow_blocks(sdbv_ctx *ctx, Table *t, uint64_t n,
+                                 uint64_t row0, uint64_t nb,
+                                 const uint32_t *blist) {
+	const Shadow &sh = t->sh;
+	const uint64_t sn_pad = sh.sn_pad;
+	if (nb == 0)
+		return;
+	switch (sh.kind) {
+	case 1: { // one lane per PF_ROWS_PER_LANE rows
+		uint64_t groups = nb * (256 / PF_ROWS_PER_LANE);
+		hipLaunchKernelGGL(k_shadow, dim3((uint32_t)((groups + 255) / 256)),
+		                   dim3(256), 0, ctx->stream, t->cm, t->norms,
+		                   (uint16_t *)sh.codes, sh.pinv(), n, t->n_pad,
+		                   sn_pad, t->d, row0, blist, (uint32_t)nb);
+		break;
+	}
+	case 2: // one lane per row
+		hipLaunchKernelGGL(k_shadow_i8, dim3((uint32_t)nb), dim3(256), 0,
+		                   ctx->stream, t->cm, t->norms, (uint8_t *)sh.codes,
+		                   sh.pscale(), sh.peps(), n, t->n_pad, sn_pad, t->d,
+		                   row0, blist);
+		break;
+	case 3:
+		hipLaunchKernelGGL(k_shadow_i6, dim3((uint32_t)nb), dim3(256), 0,
+		                   ctx->stream, t->cm, t->norms, sh.plane_h(),
+		                   sh.plane_l(t->d), sh.pscale(), sh.peps(), sh.xsum(),
+		                   sh.peps4(), sh.xsum_h(), n, t->n_pad, sn_pad, t->d,
+		                   row0, blist);
+		break;
+	case 5: // one lane per row
+		hipLaunchKernelGGL(k_shadow_l2, dim3((uint32_t)nb), dim3(256), 0,
+		                   ctx->stream, t->cm, (uint8_t *)sh.codes,
+		                   sh.pscale(), sh.l2_xx(), sh.l2_res(), n, t->n_pad,
+		                   sn_pad, t->d, row0, blist);
+		break;
+	}
+}
+
 // Launch the shadow builder of t->sh over rows [row0, row_end), both
 // multiples of 256 with row_end <= sn_pad (the bf16 builder's last block may
 // run on to sn_pad, its own guard): the whole shadow when staging or growth
@@ -4355,40 +4558,7 @@ static uint64_t shadow_code_bytes(int kind, uint32_t d, uint64_t sn_pad) {
 // the count it is about to commit.
 static void launch_shadow_rows(sdbv_ctx *ctx, Table *t, uint64_t n,
                                uint64_t row0, uint64_t row_end) {
-	const Shadow &sh = t->sh;
-	const uint64_t sn_pad = sh.sn_pad;
-	const uint64_t rows = row_end - row0;
-	if (rows == 0)
-		return;
-	switch (sh.kind) {
-	case 1: { // one lane per PF_ROWS_PER_LANE rows
-		uint64_t groups = rows / PF_ROWS_PER_LANE;
-		hipLaunchKernelGGL(k_shadow, dim3((uint32_t)((groups + 255) / 256)),
-		                   dim3(256), 0, ctx->stream, t->cm, t->norms,
-		                   (uint16_t *)sh.codes, sh.pinv(), n, t->n_pad,
-		                   sn_pad, t->d, row0);
-		break;
-	}
-	case 2: // one lane per row
-		hipLaunchKernelGGL(k_shadow_i8, dim3((uint32_t)(rows / 256)),
-		                   dim3(256), 0, ctx->stream, t->cm, t->norms,
-		                   (uint8_t *)sh.codes, sh.pscale(), sh.peps(), n,
-		                   t->n_pad, sn_pad, t->d, row0);
-		break;
-	case 3:
-		hipLaunchKernelGGL(k_shadow_i6, dim3((uint32_t)(rows / 256)),
-		                   dim3(256), 0, ctx->stream, t->cm, t->norms,
-		                   sh.plane_h(), sh.plane_l(t->d), sh.pscale(),
-		                   sh.peps(), sh.xsum(), sh.peps4(), sh.xsum_h(), n,
-		                   t->n_pad, sn_pad, t->d, row0);
-		break;
-	case 5: // one lane per row
-		hipLaunchKernelGGL(k_shadow_l2, dim3((uint32_t)(rows / 256)),
-		                   dim3(256), 0, ctx->stream, t->cm,
-		                   (uint8_t *)sh.codes, sh.pscale(), sh.l2_xx(),
-		                   sh.l2_res(), n, t->n_pad, sn_pad, t->d, row0);
-		break;
-	}
+	launch_shadow_blocks(ctx, t, n, row0, (row_end - row0) / 256, nullptr);
 }
 
 static int build_shadow(sdbv_ctx *ctx, Table *t, int kind, bool h4 = false) {
@@ -6245,6 +6415,119 @@ int sdbv_append_rows(sdbv_ctx *ctx, uint64_t table, const float *rows,
 	ctx->stats.last_append_kernel_ms = kernel_ms;
 	ctx->stats.last_append_realloc = regrow ? 1u : 0u;
 	ctx->stats.last_append_ms =
+	    std::chrono::duration<double, std::milli>(
+	        std::chrono::steady_clock::now() - t_start)
+	        .count();
+	return SDBV_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Updating staged rows in place
+// ---------------------------------------------------------------------------
+uint64_t sdbv_update_blocks(const uint32_t *row_idx, uint64_t m,
+                            uint32_t *out_blocks, uint64_t cap) {
+	uint64_t count = 0;
+	for (uint64_t i = 0; i < m; i++) {
+		const uint32_t b = row_idx[i] / 256;
+		if (i && b == row_idx[i - 1] / 256)
+			continue;
+		if (count < cap)
+			out_blocks[count] = b;
+		count++;
+	}
+	return count;
+}
+
+int sdbv_update_rows(sdbv_ctx *ctx, uint64_t table, const uint32_t *row_idx,
+                     const float *rows, uint64_t m, uint32_t d) {
+	auto t_start = std::chrono::steady_clock::now();
+	std::lock_guard<std::mutex> lk(ctx->mu);
+	auto it = ctx->tables.find(table);
+	if (it == ctx->tables.end())
+		return SDBV_ERR_NO_TABLE;
+	Table *t = &it->second;
+	if (!t->scan_table)
+		return SDBV_ERR_UNSUPPORTED;
+	if (d != t->d)
+		return SDBV_ERR_BAD_ARG;
+	if (m == 0)
+		return SDBV_OK;
+	if (!rows || !row_idx)
+		return SDBV_ERR_BAD_ARG;
+	// strictly increasing and below n: no position twice, so m <= n
+	for (uint64_t i = 0; i < m; i++)
+		if (row_idx[i] >= t->n || (i && row_idx[i] <= row_idx[i - 1]))
+			return SDBV_ERR_BAD_ARG;
+
+	// the touched 256-row blocks of the shadow, uploaded once behind the
+	// largest chunk
+	std::vector<uint32_t> blocks;
+	if (t->sh.kind) {
+		blocks.resize(sdbv_update_blocks(row_idx, m, nullptr, 0));
+		(void)sdbv_update_blocks(row_idx, m, blocks.data(), blocks.size());
+	}
+	const uint64_t row_bytes = (uint64_t)d * sizeof(float);
+	const uint64_t chunk_rows =
+	    std::max<uint64_t>(1, APPEND_CHUNK_BYTES / row_bytes);
+	const uint64_t list_off =
+	    std::min(m, chunk_rows) * (row_bytes + sizeof(uint32_t));
+	int rc = ensure_cap(ctx, &ctx->app_buf, &ctx->app_buf_cap,
+	                    list_off + blocks.size() * sizeof(uint32_t));
+	if (rc != SDBV_OK)
+		return rc;
+	float *rm = (float *)ctx->app_buf;
+	uint32_t *blist = (uint32_t *)((char *)ctx->app_buf + list_off);
+	if (!blocks.empty())
+		HIP_CHECK(ctx, hipMemcpyAsync(blist, blocks.data(),
+		                              blocks.size() * sizeof(uint32_t),
+		                              hipMemcpyHostToDevice, ctx->stream));
+	double kernel_ms = 0;
+	for (uint64_t done = 0; done < m;) {
+		const uint64_t c = std::min(chunk_rows, m - done);
+		uint32_t *idb = (uint32_t *)((char *)ctx->app_buf + c * row_bytes);
+		HIP_CHECK(ctx, hipMemcpyAsync(rm, rows + done * d, c * row_bytes,
+		                              hipMemcpyHostToDevice, ctx->stream));
+		HIP_CHECK(ctx, hipMemcpyAsync(idb, row_idx + done, c * sizeof(uint32_t),
+		                              hipMemcpyHostToDevice, ctx->stream));
+		HIP_CHECK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+		hipLaunchKernelGGL(k_update_rows, dim3((uint32_t)((c + 63) / 64)),
+		                   dim3(64), 0, ctx->stream, rm, idb, t->cm, t->norms,
+		                   t->aux, c, t->n_pad, d, (int)t->metric);
+		done += c;
+		if (done == m) {
+			// the shadow over exactly the touched blocks, one launch; then the
+			// batch header again from aux (and norms): the fold the append
+			// continues cannot forget the row that held the maximum, or a row
+			// that had no key and now has one
+			launch_shadow_blocks(ctx, t, t->n, 0, blocks.size(), blist);
+			if (t->bunc) {
+				BatchAuxHdr *hdr = (BatchAuxHdr *)(t->bunc + BATCH_UNC_CAP);
+				HIP_CHECK(ctx, hipMemsetAsync(hdr, 0, sizeof(BatchAuxHdr),
+				                              ctx->stream));
+				const uint64_t nb = std::min<uint64_t>(
+				    (t->n + THREADS - 1) / THREADS, REFOLD_MAX_BLOCKS);
+				hipLaunchKernelGGL(k_aux_refold, dim3((uint32_t)nb),
+				                   dim3(THREADS), 0, ctx->stream, t->aux,
+				                   t->norms, t->n, t->bunc, hdr);
+			}
+		}
+		HIP_CHECK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+		HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+		HIP_CHECK(ctx, hipGetLastError());
+		float ms = 0;
+		(void)hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1);
+		kernel_ms += ms;
+	}
+	if (t->bunc) { // as finish_stage reads them
+		BatchAuxHdr h;
+		HIP_CHECK(ctx, hipMemcpy(&h, t->bunc + BATCH_UNC_CAP, sizeof(h),
+		                         hipMemcpyDeviceToHost));
+		t->bunc_n = h.n_unc;
+		std::memcpy(&t->bmax_norm, &h.max_norm_bits, sizeof(double));
+	}
+	ctx->stats.last_update_kernel_ms = kernel_ms;
+	ctx->stats.last_update_blocks = blocks.size();
+	ctx->stats.last_update_ms =
 	    std::chrono::duration<double, std::milli>(
 	        std::chrono::steady_clock::now() - t_start)
 	        .count();
